@@ -19,6 +19,11 @@ Workload per step and rank (weak scaling: per-GPU work is fixed as N grows):
 
 Usage:  python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B] ...
         (N>1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N)
+
+A plain run sets up, warms up, times the K steps and prints the result line.  `--dump-outputs DIR`
+also writes what the last timed step computed (see dump_outputs); inputs and initial weights are
+seeded, so two builds run with the same arguments can be compared array for array.  `--full` adds
+what the headline figure does not need (the first batch's dedup statistics on stderr).
 """
 
 from __future__ import annotations
@@ -67,6 +72,39 @@ PRESETS = {
 }
 
 
+DUMP_ROWS = 8192  # rows per sample of --dump-outputs (k=128 + FTRL: 3 arrays of 2 x 8192 x 129 fp32, 25 MB)
+
+
+def dump_outputs(out_dir: str, model, last, batch) -> None:
+    """``--dump-outputs``: what the last timed ``train_step`` handed back and left behind, as .npy.
+
+    * ``loss_sum``  [1] float64: the step's summed loss (``StepOut.loss_sum``);
+    * ``row_ids``   [n] float64: global ids of the sampled rows this rank owns -- ``DUMP_ROWS`` of the
+      rows that step's batch touched and ``DUMP_ROWS`` drawn over the whole vocabulary, both with a
+      fixed seed (the same ids for the same arguments);
+    * ``rows``      [n, k+1] float32: those rows after the step, reference layout (col 0 = w, 1..k = v,
+      bf16 / fp8 rows dequantised);
+    * ``slot0`` (, ``slot1``) [n, k+1] float32: their optimizer slots (Adagrad accumulator / FTRL n, z).
+    """
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    t = model.table
+    g = torch.Generator().manual_seed(20240607)
+    touched = torch.unique(batch.ids.long()).cpu()
+    pick = touched[torch.randint(0, touched.numel(), (DUMP_ROWS,), generator=g)]
+    ids = torch.cat([pick, torch.randint(0, t.vocab_size, (DUMP_ROWS,), generator=g)])
+    ids = ids[ids % t.world == t.rank]
+    local = (ids // t.world).to(t.device)
+    arrays = {"loss_sum": last.loss_sum.detach().double().reshape(1), "row_ids": ids.double(),
+              "rows": t.reference_rows(local)}
+    for name, sw, sv in (("slot0", t.s0w, t.s0v), ("slot1", t.s1w, t.s1v)):
+        if sv is not None:
+            arrays[name] = torch.cat([sw[local].unsqueeze(1), sv[local, : t.K].float()], dim=1)
+    for name, x in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), x.cpu().numpy())
+
+
 def main() -> int:
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--gpus", type=int, default=1)
@@ -95,6 +133,11 @@ def main() -> int:
     ap.add_argument("--graph", type=int, default=0,
                     help="local step: 0 = eager lookahead pipeline (next batch's dedup overlaps this step; "
                          "measured fastest), 1 = the same pipeline as a hipGraph ring")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed (its loss and a fixed, "
+                         "seeded sample of the table rows and optimizer slots it left) as DIR/<name>.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need (the first batch's dedup statistics)")
     a = ap.parse_args()
 
     p = dict(PRESETS[a.preset])
@@ -164,7 +207,7 @@ def main() -> int:
         pool = bufs
         torch.cuda.synchronize()
         graphed = True
-    if rank == 0:
+    if a.full and rank == 0:  # (a dedup of its own, outside the timed path)
         from fast_tffm_amd.ops import kernels as Kd
 
         dd = Kd.dedup(pool[0].ids if pool[0].ids.dtype == torch.int32 else pool[0].ids.int(), key_bits=32)
@@ -211,6 +254,11 @@ def main() -> int:
     comm_backend = tdist.get_backend(ctx.group) if (ctx.group is not None and tdist.is_initialized()) else None
 
     loss = last.mean_loss() if last is not None else float("nan")
+    if a.dump_outputs and last is not None:
+        model.flush()  # (bounded staleness: the pending gradient is applied, on every rank)
+        if rank == 0:
+            dump_outputs(a.dump_outputs, model, last, pool[(a.warmup + a.steps - 1) % len(pool)])
+        ctx.barrier()
     if a.profile_steps and rank == 0:
         from fast_tffm_amd.utils.trace import profile_steps
 

@@ -1,4 +1,6 @@
+import gzip
 import os
+import shutil
 import sys
 
 import pytest
@@ -10,7 +12,8 @@ if ROOT not in sys.path:
 # Index range checks on every kernel launch in tests (host sync per op: fine here).
 os.environ.setdefault("FM_DEBUG_CHECKS", "1")
 
-REF_DATA = "/root/reference/data"
+# The reference's sample.cfg and heads of its sample data set (tests/golden/README.md).
+GOLDEN_REF = os.path.join(ROOT, "tests", "golden", "reference")
 
 
 def pytest_configure(config):
@@ -37,7 +40,18 @@ def pytest_collection_modifyitems(config, items):
 
 
 @pytest.fixture(scope="session")
-def ref_data_dir():
-    if not os.path.isdir(REF_DATA):
-        pytest.skip("reference data directory not available")
-    return REF_DATA
+def ref_sample_dir(tmp_path_factory):
+    """The reference's sample.cfg next to its data/ files, unpacked from tests/golden/reference."""
+    d = tmp_path_factory.mktemp("reference")
+    shutil.copy(os.path.join(GOLDEN_REF, "sample.cfg"), d / "sample.cfg")
+    (d / "data").mkdir()
+    for name in sorted(os.listdir(os.path.join(GOLDEN_REF, "data"))):
+        assert name.endswith(".gz"), name
+        with gzip.open(os.path.join(GOLDEN_REF, "data", name), "rb") as f, open(d / "data" / name[:-3], "wb") as g:
+            shutil.copyfileobj(f, g)
+    return str(d)
+
+
+@pytest.fixture(scope="session")
+def ref_data_dir(ref_sample_dir):
+    return os.path.join(ref_sample_dir, "data")

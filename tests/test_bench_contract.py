@@ -33,6 +33,41 @@ def test_bench_prints_one_json_line(args):
     assert {"model", "global_batch", "seq_len", "parallelism"} <= set(d["config"])
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """``--dump-outputs DIR``: the last timed step's loss and a seeded sample of the rows and optimizer
+    slots it left, float32 / float64 .npy well under 64 MB, for the same rows and with the same values
+    from run to run; the timed steps still number ``--steps``.  ``--full`` adds the batch statistics (on
+    stderr) that a plain run no longer computes; stdout stays the one JSON line either way."""
+    import numpy as np
+
+    args = ["--steps", "3", "--warmup", "1", "--batch", "256", "--slots-per-gpu", "20000"]
+    env = dict(os.environ, CUDA_VISIBLE_DEVICES="", HIP_VISIBLE_DEVICES="")
+    runs = []
+    for name, extra in (("a", []), ("b", ["--full"])):
+        out = tmp_path / name
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + args + ["--dump-outputs", str(out)]
+                           + extra, capture_output=True, text=True, timeout=600, env=env)
+        assert r.returncode == 0, r.stderr[-3000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.strip()]
+        assert len(lines) == 1, r.stdout
+        d = json.loads(lines[0])
+        assert KEYS <= set(d) and d["steps"] == 3 and d["ms_per_step"] > 0
+        assert ("batch stats:" in r.stderr) == bool(extra)
+        arrays = {f[:-4]: np.load(out / f) for f in sorted(os.listdir(out))}
+        assert set(arrays) == {"loss_sum", "row_ids", "rows", "slot0"}
+        assert all(x.dtype in (np.float32, np.float64) for x in arrays.values())
+        assert sum(x.nbytes for x in arrays.values()) <= 64 * 2**20
+        runs.append(arrays)
+    a, b = runs
+    n = a["row_ids"].shape[0]
+    assert n == 2 * 8192 and a["rows"].shape == (n, 65) and a["slot0"].shape == (n, 65)
+    assert a["loss_sum"].shape == (1,) and np.isfinite(a["loss_sum"]).all() and np.isfinite(a["rows"]).all()
+    assert (a["slot0"] > 0.1).any()  # (sampled rows of the last batch: their accumulators moved)
+    assert np.array_equal(a["row_ids"], b["row_ids"])
+    for k in ("loss_sum", "rows", "slot0"):  # (CPU kernels: OpenMP may reorder fp32 sums between runs)
+        np.testing.assert_allclose(a[k], b[k], rtol=1e-5, atol=1e-8)
+
+
 def test_bench_two_ranks_one_json_line():
     """The driver's N>1 launch (torch.distributed.run, one process per device, 127.0.0.1):
     stdout holds exactly rank 0's JSON line (the gloo side-group's connection messages and

@@ -94,11 +94,8 @@ def test_config_parity_and_echo(workdir):
     assert len(c.train_files) == 2 and len(c.weight_files) == 2 and c.predict_files
 
 
-def test_reference_sample_cfg_loads():
-    p = "/root/reference/sample.cfg"
-    if not os.path.exists(p):
-        pytest.skip("reference sample.cfg not available")
-    c = load_config(p, echo=False)
+def test_reference_sample_cfg_loads(ref_sample_dir):
+    c = load_config(os.path.join(ref_sample_dir, "sample.cfg"), echo=False)
     assert (c.vocabulary_size, c.vocabulary_block_num, c.factor_num) == (800000, 10, 100)
     assert (c.batch_size, c.num_epochs, c.save_steps, c.loss_type) == (50000, 20, 10, "mse")
     assert len(c.train_files) == 5 and len(c.weight_files) == 5  # resolved next to the cfg
