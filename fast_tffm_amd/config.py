@@ -23,7 +23,10 @@ Extensions (new keys, all optional):
                 ftrl.initial_accumulator, parse_threads, loader = native|python, gpu_parse = true|false,
                 device_cache = auto|true|false, stochastic_rounding = true|false,
                 shuffle = true|false,
-                max_steps, dedup_chunk, log_steps
+                max_steps, dedup_chunk, log_steps,
+                validation_auc = true|false (exact weighted ROC AUC of the validation scores, printed and logged
+                                after the validation loss; default false), auc_tolerance = <float> (stop when
+                                the validation AUC is >= it; needs validation_auc and validation_files)
   [Distributed] mode = auto|local|shard|dp|dp_dense, grad_reduce = sum|mean,
                 comm_dtype = auto|fp32|bf16 (row-sharded wire rows; auto = table storage dtype),
                 microbatches = 1|2|... (row-sharded step parts overlapping the exchange; default 1),
@@ -107,6 +110,8 @@ class FMRunConfig:
     dedup_chunk: int = 32
     global_bias: bool = False
     log_steps: int = 1
+    validation_auc: bool = False        # report the exact weighted ROC AUC next to the validation loss
+    auc_tolerance: float | None = None  # stop when the validation AUC is >= this
     # [Predict]
     predict_files: list[str] = field(default_factory=list)
     # [Distributed]
@@ -219,6 +224,8 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
     c.max_steps = opt(TRAIN, "max_steps", int, c.max_steps)
     c.dedup_chunk = opt(TRAIN, "dedup_chunk", int, c.dedup_chunk)
     c.log_steps = opt(TRAIN, "log_steps", int, c.log_steps)
+    c.validation_auc = opt(TRAIN, "validation_auc", to_bool, c.validation_auc)
+    c.auc_tolerance = opt(TRAIN, "auc_tolerance", float, c.auc_tolerance)
 
     if c.loss_type not in ("logistic", "mse"):
         raise ConfigError("loss_type must be 'logistic' or 'mse', got %r" % c.loss_type)
@@ -243,6 +250,8 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
         c.validation_weight_files = _expand(vwf, base_dir)
         if len(c.validation_data_files) != len(c.validation_weight_files):
             raise ConfigError("The numbers of validation data files and validation weight files do not match.")
+    if c.auc_tolerance is not None and not (c.validation_auc and c.validation_data_files):
+        raise ConfigError("auc_tolerance needs validation_auc = true and validation_files.")
 
     pf = read_list(PREDICT, "predict_files", required=False)
     if pf is not None:

@@ -251,6 +251,51 @@ void csr_rows(int B, const int* offsets, int* ex_of_occ) {
 }
 
 namespace {
+// One pass over the (key, index) order: a run of equal keys with positive weight rp and negative weight rn
+// after negatives of weight nlt adds rp * (nlt + (nlt + rn)).
+template <typename T>
+void auc_pass(const std::vector<uint64_t>& kv, const float* labels, const float* weights, uint64_t nans, T* out) {
+  const size_t n = kv.size();
+  T u2 = 0, p = 0, nlt = 0;
+  for (size_t j = 0; j < n;) {
+    const uint32_t key = static_cast<uint32_t>(kv[j] >> 32);
+    T rp = 0, rn = 0;
+    for (; j < n && static_cast<uint32_t>(kv[j] >> 32) == key; ++j) {
+      const uint32_t i = static_cast<uint32_t>(kv[j]);
+      const T w = weights ? static_cast<T>(weights[i]) : static_cast<T>(1);
+      if (labels[i] > 0.f) rp += w;
+      else rn += w;
+    }
+    const T nle = nlt + rn;
+    u2 += rp * (nlt + nle);
+    p += rp;
+    nlt = nle;
+  }
+  out[0] = u2;
+  out[1] = p;
+  out[2] = nlt;
+  out[3] = static_cast<T>(nans);
+  out[4] = 0;
+}
+}  // namespace
+
+void auc(int n, const float* scores, const float* labels, const float* weights, void* out) {
+  std::vector<uint64_t> kv(n > 0 ? n : 0);
+  uint64_t nans = 0;
+  for (int j = 0; j < n; ++j) {
+    uint32_t b;
+    std::memcpy(&b, scores + j, 4);  // (bit patterns: no arithmetic on the score, denormals keep their order)
+    nans += (b & 0x7fffffffu) > 0x7f800000u;
+    if (b == 0x80000000u) b = 0u;    // -0.0 == +0.0
+    const uint32_t key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    kv[j] = (static_cast<uint64_t>(key) << 32) | static_cast<uint32_t>(j);
+  }
+  std::sort(kv.begin(), kv.end());
+  if (weights) auc_pass<double>(kv, labels, weights, nans, static_cast<double*>(out));
+  else auc_pass<uint64_t>(kv, labels, weights, nans, static_cast<uint64_t*>(out));
+}
+
+namespace {
 inline float init_uniform(unsigned long long seed, long long gid, int col, float range) {
   const unsigned long long h =
       mix64(seed ^ mix64(static_cast<unsigned long long>(gid) * 0x100000001b3ull + static_cast<unsigned long long>(col)));

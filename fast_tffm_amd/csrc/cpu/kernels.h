@@ -42,6 +42,10 @@ void apply_rows(int U, const int* seg_start, const int* uniq, const int* perm, c
 
 void csr_rows(int B, const int* offsets, int* ex_of_occ);
 
+// Exact weighted ROC AUC statistics (hip/auc.hip: same definition, same two modes): out[5] = U2, P, N, NaN
+// scores, 0 -- uint64 when weights is null (exact), else fp64 summed in sorted order.
+void auc(int n, const float* scores, const float* labels, const float* weights, void* out);
+
 // Counter-based U(-range, range) init, identical to the gfx950 init_rows kernel.
 void init_rows(void* v, long long v_stride, float* w, long long w_stride, long long rows, int K, int Kp, int dtype,
                long long gid_mul, long long gid_add, unsigned long long seed, float range, int threads);

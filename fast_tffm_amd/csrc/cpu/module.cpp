@@ -408,4 +408,12 @@ PYBIND11_MODULE(_fm_cpu, m) {
       "csr_rows",
       [](int B, u64 offsets, u64 ex_of_occ) { fm::cpu::csr_rows(B, P<const int>(offsets), P<int>(ex_of_occ)); },
       py::arg("B"), py::arg("offsets"), py::arg("ex_of_occ"));
+
+  m.def(
+      "auc",
+      [](int n, u64 scores, u64 labels, u64 weights, u64 out) {
+        py::gil_scoped_release nogil;
+        fm::cpu::auc(n, P<const float>(scores), P<const float>(labels), P<const float>(weights), P<void>(out));
+      },
+      py::arg("n"), py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("out"));
 }

@@ -24,6 +24,7 @@ using u64 = std::uintptr_t;
 #include "fm_bwd.hip"
 #include "fm_fwd.hip"
 #include "dedup.hip"
+#include "auc.hip"
 #include "shard.hip"
 #include "init.hip"
 #include "parse.hip"
@@ -243,6 +244,25 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       py::arg("vals"), py::arg("sorted_x"), py::arg("payload_is_ex"), py::arg("ex_shift"), py::arg("offsets"),
       py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"), py::arg("ids") = 0, py::arg("kW") = 1,
       py::arg("kRps") = 0, py::arg("gen_codes") = 0, py::arg("B") = 0);
+
+  m.def(
+      "auc_workspace_bytes",
+      [](long long n) {
+        const size_t b = fm::auc_workspace_bytes(n);
+        if (!b) throw std::invalid_argument("auc: n must be in [0, 2^30)");
+        return b;
+      },
+      py::arg("n"));
+  m.def(
+      "auc",  // AUC statistics [U2, P, N, nan count, sort error word] into out[5]: int64 (weights == 0) or fp64;
+              // asynchronous: the caller reads the error word with the record (ops/kernels.py AucStats)
+      [](u64 scores, u64 labels, u64 weights, int n, u64 out, u64 ws, size_t ws_bytes, u64 stream) {
+        check(fm::launch_auc(P<const float>(scores), P<const float>(labels), P<const float>(weights), n, P<void>(out),
+                             P<void>(ws), ws_bytes, S(stream)),
+              "auc");
+      },
+      py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("n"), py::arg("out"), py::arg("ws"),
+      py::arg("ws_bytes"), py::arg("stream"));
 
   m.def(
       "gather_rows",

@@ -385,7 +385,7 @@ def check_device_errors(device: torch.device | None = None, clear: bool = True) 
     with torch.cuda.device(device if device is not None else torch.cuda.current_device()):
         err = int(native.hip().device_errors(clear))
     if err:
-        what = ["radix sort look-back spin bound hit (a dedup plan was invalid)"] if err & DEV_ERR_SORT else []
+        what = ["radix sort look-back spin bound hit (a dedup plan or AUC was invalid)"] if err & DEV_ERR_SORT else []
         raise RuntimeError(f"device error word {err:#x}: {'; '.join(what) or 'unknown'}")
 
 
@@ -415,6 +415,7 @@ def _sort_selfcheck(dev: torch.device) -> None:
         import warnings
 
         h.set_sort_algo(0)
+        _SORT_UNSTABLE.add(dev.index)
         warnings.warn("in-tree radix sort failed its stability self-check on this device: the dedup uses "
                       "rocPRIM's sort (FM_SORT=rocprim)")
 
@@ -770,6 +771,92 @@ def fm_backward(dd: DedupOut, dpred: torch.Tensor, r1: torch.Tensor, Kp: int, *,
                          l1=float(o.l1), l2=float(o.l2), beta=float(o.beta), grad_out=gptr, g_stride=gstride,
                          dtype=dt, threads=threads)
     return grad_out
+
+
+# ---------------------------------------------------------------------------
+# validation metric: exact weighted ROC AUC
+# ---------------------------------------------------------------------------
+class AucStats:
+    """The record of one ``auc`` call, on the op's device: ``[U2, P, N, NaN scores, sort error word]`` --
+    int64 (unweighted: exact) or float64 (weighted).  ``stats()`` / ``value()`` read it (a host sync on
+    the GPU) and raise when the GPU sort reported a failed look-back: never a number then."""
+
+    __slots__ = ("rec", "weighted", "n", "done")
+
+    def __init__(self, rec: torch.Tensor, weighted: bool, n: int, done: "torch.cuda.Event | None" = None):
+        self.rec, self.weighted, self.n = rec, weighted, n
+        self.done = done  # GPU: recorded behind the launch chain, on its stream
+
+    def stats(self) -> tuple:
+        """(U2, P, N, nans) on the host: Python ints (unweighted) or floats and the int NaN count."""
+        if self.done is not None:  # (the reader's current stream need not be the chain's)
+            self.done.synchronize()
+        u2, p, n, nans, err = self.rec.tolist()
+        if err:
+            raise RuntimeError(f"auc: the radix sort's look-back spin bound was hit (error word {int(err)}); "
+                               "no AUC for this input")
+        return u2, p, n, int(nans)
+
+    def value(self) -> float:
+        """U2 / (2 P N); NaN when a score is NaN or a class has no weight (undefined, not an error)."""
+        u2, p, n, nans = self.stats()
+        if nans or not p > 0 or not n > 0:
+            return float("nan")
+        return u2 / (2 * p * n)
+
+
+_SORT_UNSTABLE: set = set()  # devices whose in-tree sort failed _sort_selfcheck
+
+
+def auc_workspace(n: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of ``auc`` for up to ``n`` scores (GPU)."""
+    return torch.empty(int(native.hip().auc_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def auc(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None = None, *,
+        ws: torch.Tensor | None = None) -> AucStats:
+    """Exact weighted ROC AUC statistics of raw scores (logits: the sigmoid is monotone).
+
+    An example is positive iff ``label > 0`` (0/1 and -1/+1 labels alike); ``weights`` None = all ones.
+    With P / N the weight of the positives / negatives, U2 = sum over positives of w_i (Nlt(s_i) +
+    Nle(s_i)) (Nlt / Nle: weight of the negatives with a score below / not above s_i) and AUC = U2 /
+    (2 P N): a positive-negative tie counts one half.  Scores compare as IEEE fp32 values (-0.0 == +0.0,
+    infinities and denormals ordered as usual); NaN scores are counted and make the AUC NaN.
+    Unweighted statistics are integers (exact, the same on GPU and CPU); weighted ones are fp64 sums in a
+    fixed order (bitwise the same run to run).  GPU: hip/auc.hip on the current stream (``ws``: reusable
+    ``auc_workspace``); CPU: a sort and one pass.  ``n == 0`` launches nothing (NaN).
+    """
+    dev = scores.device
+    n = scores.numel()
+    _chk_vec(scores, torch.float32, n, "scores", dev)
+    _chk_vec(labels, torch.float32, n, "labels", dev)
+    _chk_vec(weights, torch.float32, n, "weights", dev)
+    _check(labels.numel() == n and (weights is None or weights.numel() == n), "auc: one label / weight per score")
+    _check(n < 2**30, "auc: n must be < 2^30 (the radix sort's bound)")
+    weighted = weights is not None
+    if _DEBUG and weighted and n > 0 and not (scores.is_cuda and torch.cuda.is_current_stream_capturing()):
+        _check(bool(weights.min() >= 0), "weights: must be >= 0")
+    rdt = torch.float64 if weighted else torch.int64
+    if n == 0:
+        return AucStats(torch.zeros(5, dtype=rdt), weighted, 0)  # (a host record: nothing is launched)
+    rec = torch.empty(5, dtype=rdt, device=dev)
+    if _is_gpu(scores):
+        h = native.hip()
+        _sort_selfcheck(dev)
+        if dev.index in _SORT_UNSTABLE:
+            raise RuntimeError("auc: the in-tree radix sort failed its stability self-check on this device")
+        need = int(h.auc_workspace_bytes(n))
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _chk_vec(ws, torch.uint8, need, "ws", dev)
+        h.auc(scores=_p(scores), labels=_p(labels), weights=_p(weights), n=n, out=_p(rec), ws=_p(ws),
+              ws_bytes=ws.numel(), stream=_stream(scores))
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        return AucStats(rec, weighted, n, done)
+    _check(ws is None, "auc: the workspace is a GPU argument")
+    native.cpu().auc(n=n, scores=_p(scores), labels=_p(labels), weights=_p(weights), out=_p(rec))
+    return AucStats(rec, weighted, n)
 
 
 # ---------------------------------------------------------------------------

@@ -196,6 +196,36 @@ def local_context(device: str | torch.device = "cpu") -> DistContext:
     return DistContext(rank=0, world=1, local_rank=0, device=dev, backend="none")
 
 
+def gather_dealt(ctx: DistContext | None, parts: list[torch.Tensor | None]) -> list[torch.Tensor | None]:
+    """Undo a ``rank::world`` deal of equally long fp32 vectors (the validation split, trainer.load_validation):
+    every rank passes its slices (``None`` entries -- the same on every rank -- stay ``None``) and gets
+    the full vectors back, in the original order.  The slices are padded to the longest one for the
+    all-gather over ``ctx.group`` (gloo or RCCL) and the padding is stripped by the gathered slice
+    lengths: no padding value ever reaches the result."""
+    if ctx is None or ctx.world == 1:
+        return list(parts)
+    have = [p for p in parts if p is not None]
+    n = have[0].numel()
+    if any(p.dtype != torch.float32 or p.dim() != 1 or p.numel() != n for p in have):
+        raise ValueError("gather_dealt: fp32 vectors of one length")
+    sizes = [torch.zeros(1, dtype=torch.int64, device=ctx.device) for _ in range(ctx.world)]
+    dist.all_gather(sizes, torch.tensor([n], dtype=torch.int64, device=ctx.device), group=ctx.group)
+    sizes = [int(s) for s in torch.cat(sizes).tolist()]
+    total, m = sum(sizes), max(sizes)
+    if sizes != [len(range(r, total, ctx.world)) for r in range(ctx.world)]:
+        raise ValueError(f"gather_dealt: slice lengths {sizes} are not a rank::world deal of {total}")
+    mine = torch.zeros((len(have), m), dtype=torch.float32, device=ctx.device)
+    for k, p in enumerate(have):
+        mine[k, :n] = p.to(ctx.device)
+    got = [torch.empty_like(mine) for _ in range(ctx.world)]
+    dist.all_gather(got, mine, group=ctx.group)
+    full = torch.empty((len(have), total), dtype=torch.float32, device=ctx.device)
+    for r in range(ctx.world):
+        full[:, r::ctx.world] = got[r][:, :sizes[r]]
+    rows = iter(full.unbind(0))
+    return [None if p is None else next(rows).contiguous() for p in parts]
+
+
 def shutdown() -> None:
     """Close every live model / exchange (their communicators, streams and hipGraphs are
     released in a fixed order while the process groups still exist), then destroy the

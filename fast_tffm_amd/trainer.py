@@ -5,7 +5,8 @@ Reference behaviour kept (run_tffm.py:10-90, :213-231):
 * ``-m``: ``speed: <ex/s> shuffle_queue: x% example_queue: y%`` per step;
 * every ``save_steps``: validation loss ``validation loss at step %d: %.8f`` and
   early stop below ``tolerance`` ("Loss on validation data set is below
-  tolerance. Training completed."), checkpoint (CheckpointSaverHook);
+  tolerance. Training completed."), checkpoint (CheckpointSaverHook); with ``validation_auc`` (new) also
+  ``validation auc at step %d: %.8f`` and an early stop at ``auc_tolerance``;
 * automatic restore of the latest checkpoint in ``log_dir`` (MonitoredTrainingSession);
 * end: ``Average speed:  <ex/s>  ex/s`` and ``Model saved to  <log_dir>``;
 * ``-t FILE``: chrome-trace timeline (reference: first step only; here the
@@ -31,8 +32,8 @@ from .utils.fault import maybe_inject
 from .utils.trace import roctx_range
 from .data.reader import NativeTextReader, Prefetcher, ReaderState, TextBatchReader, load_file_batch
 from .models.fm import FactorizationMachine
-from .ops.kernels import check_device_errors
-from .parallel.dist import DistContext
+from .ops.kernels import auc, check_device_errors
+from .parallel.dist import DistContext, gather_dealt
 from .utils import checkpoint as ckpt
 from .utils.metrics import MetricsLogger
 
@@ -163,6 +164,17 @@ class Trainer:
         fo = self.model.forward(vb, loss=self.cfg.loss_type)
         return self._global_loss(float(fo.loss_sum), vb.B)
 
+    def validation_metrics(self, vb) -> tuple[float, float]:
+        """(validation loss, validation ROC AUC) from ONE forward: the loss as ``validation_loss`` gives
+        it, the AUC (ops/kernels.py ``auc``, exact and weighted like the loss) over the forward's scores.
+        Multi-rank: an exact AUC is no sum of per-rank AUCs, so every rank gathers all ranks' scores,
+        labels and weights and computes the same AUC on the full set."""
+        fo = self.model.forward(vb, loss=self.cfg.loss_type)
+        loss = self._global_loss(float(fo.loss_sum), vb.B)
+        scores, labels, weights = gather_dealt(self.ctx if self.world > 1 else None,
+                                               [fo.pred[:vb.B].contiguous(), vb.labels, vb.weights])
+        return loss, auc(scores, labels, weights).value()
+
     # ------------------------------------------------------------------
     def train(self) -> dict:
         c = self.cfg
@@ -249,11 +261,20 @@ class Trainer:
                 last_loss, tprev = report(pending)
                 pending = None
                 if vb is not None:
-                    v_loss = self.validation_loss(vb)
+                    if c.validation_auc:
+                        v_loss, v_auc = self.validation_metrics(vb)
+                    else:
+                        v_loss, v_auc = self.validation_loss(vb), None
                     self.print("validation loss at step %d: %.8f" % (step_num, v_loss))
                     metrics.log(step_num, force=True, validation_loss=v_loss)
+                    if v_auc is not None:
+                        self.print("validation auc at step %d: %.8f" % (step_num, v_auc))
+                        metrics.log(step_num, force=True, validation_auc=v_auc)
                     if c.tolerance is not None and v_loss < c.tolerance:
                         self.print("Loss on validation data set is below tolerance. Training completed.")
+                        ended_early = True
+                    if c.auc_tolerance is not None and v_auc is not None and v_auc >= c.auc_tolerance:
+                        self.print("AUC on validation data set is above tolerance. Training completed.")
                         ended_early = True
                 check_device_errors(self.device)  # (kernels' sticky error word: fail before saving)
                 if c.log_dir:
