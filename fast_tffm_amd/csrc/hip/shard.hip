@@ -224,7 +224,11 @@ struct RowUpdate {
                                     bool tact, uint32_t sr) {
     opt_step_row<TV, EPL>(a.opt, gr, vv, st0, st1);
     store_row_e<LPR, TV, EPL>(vrow, vv, a.w, row, a.w_stride, t, tact, sr);
-    if (tact) {
+    // (sgd has no state and leaves slot 0 alone: written back unconditionally, its untouched st0
+    // registers reached the store undefined on the sgd branch of the gfx950 code and the applied
+    // rows' s0v came back as garbage -- tests/test_shard_kernels_gpu.py)
+    const bool has_state = a.opt.type != kOptSgd;
+    if (tact && has_state) {
       const uint32_t col = (uint32_t)(t * EPL);
       store_state<TV, EPL>(a.s0v, soff, st0, sr ? sr ^ kSrSalt0 : 0u, (uint32_t)row, col);
       if (a.s1v) store_state<TV, EPL>(a.s1v, soff, st1, sr ? sr ^ kSrSalt1 : 0u, (uint32_t)row, col);
@@ -232,8 +236,10 @@ struct RowUpdate {
     if (t == 0) {
       opt_step_tv<TV>(a.opt, gw, pw, q0, q1);
       a.w[row * a.w_stride] = pw;
-      a.s0w[row] = q0;
-      if (a.s1w) a.s1w[row] = q1;
+      if (has_state) {
+        a.s0w[row] = q0;
+        if (a.s1w) a.s1w[row] = q1;
+      }
     }
   }
 };
