@@ -26,7 +26,9 @@ Extensions (new keys, all optional):
                 max_steps, dedup_chunk, log_steps,
                 validation_auc = true|false (exact weighted ROC AUC of the validation scores, printed and logged
                                 after the validation loss; default false), auc_tolerance = <float> (stop when
-                                the validation AUC is >= it; needs validation_auc and validation_files)
+                                the validation AUC is >= it; needs validation_auc and validation_files),
+                checkpoint_format = dense|sparse (sparse: a checkpoint stores only the rows that differ from
+                                their counter-based init, and restore regenerates the others; default dense)
   [Distributed] mode = auto|local|shard|dp|dp_dense, grad_reduce = sum|mean,
                 comm_dtype = auto|fp32|bf16 (row-sharded wire rows; auto = table storage dtype),
                 microbatches = 1|2|... (row-sharded step parts overlapping the exchange; default 1),
@@ -112,6 +114,7 @@ class FMRunConfig:
     log_steps: int = 1
     validation_auc: bool = False        # report the exact weighted ROC AUC next to the validation loss
     auc_tolerance: float | None = None  # stop when the validation AUC is >= this
+    checkpoint_format: str = "dense"    # dense (every row) | sparse (rows that differ from their init)
     # [Predict]
     predict_files: list[str] = field(default_factory=list)
     # [Distributed]
@@ -226,6 +229,9 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
     c.log_steps = opt(TRAIN, "log_steps", int, c.log_steps)
     c.validation_auc = opt(TRAIN, "validation_auc", to_bool, c.validation_auc)
     c.auc_tolerance = opt(TRAIN, "auc_tolerance", float, c.auc_tolerance)
+    c.checkpoint_format = opt(TRAIN, "checkpoint_format", lambda s: s.strip().lower(), c.checkpoint_format)
+    if c.checkpoint_format not in ("dense", "sparse"):
+        raise ConfigError(f"[Train] checkpoint_format must be dense or sparse, got {c.checkpoint_format}")
 
     if c.loss_type not in ("logistic", "mse"):
         raise ConfigError("loss_type must be 'logistic' or 'mse', got %r" % c.loss_type)

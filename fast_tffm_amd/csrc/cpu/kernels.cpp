@@ -321,5 +321,43 @@ void init_rows(void* v, long long v_stride, float* w, long long w_stride, long l
   }
 }
 
+long long changed_rows(const void* v, long long v_stride, const float* w, long long w_stride, const float* s0v,
+                        const float* s1v, long long s_stride, const float* s0w, const float* s1w, long long rows,
+                        int K, int dtype, long long gid_mul, long long gid_add, unsigned long long seed, float range,
+                        const uint32_t* sv_bits, const uint32_t* sw_bits, uint8_t* flags, int threads) {
+  set_threads(threads);
+  const auto bits = [](const float* p) {
+    uint32_t b;
+    std::memcpy(&b, p, 4);
+    return b;
+  };
+  long long count = 0;
+#pragma omp parallel for schedule(static) reduction(+ : count)
+  for (long long r = 0; r < rows; ++r) {
+    const long long gid = r * gid_mul + gid_add;
+    const float w0 = init_uniform(seed, gid, 0, range);
+    bool d = bits(w + r * w_stride) != bits(&w0);
+    d = d || (s0w && bits(s0w + r) != sw_bits[0]) || (s1w && bits(s1w + r) != sw_bits[1]);
+    for (int c = 0; c < K && !d; ++c) {
+      const float val = init_uniform(seed, gid, c + 1, range);
+      if (dtype == 1)
+        d = static_cast<const uint16_t*>(v)[r * v_stride + c] != f32_to_bf16(val);
+      else
+        d = bits(static_cast<const float*>(v) + r * v_stride + c) != bits(&val);
+      d = d || (s0v && bits(s0v + r * s_stride + c) != sv_bits[0]) ||
+          (s1v && bits(s1v + r * s_stride + c) != sv_bits[1]);
+    }
+    flags[r] = d;
+    count += d;
+  }
+  return count;
+}
+
+void changed_rows_emit(const uint8_t* flags, long long rows, long long* out) {
+  long long n = 0;
+  for (long long r = 0; r < rows; ++r)
+    if (flags[r]) out[n++] = r;
+}
+
 }  // namespace cpu
 }  // namespace fm

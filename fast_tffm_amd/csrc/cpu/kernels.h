@@ -50,5 +50,15 @@ void auc(int n, const float* scores, const float* labels, const float* weights, 
 void init_rows(void* v, long long v_stride, float* w, long long w_stride, long long rows, int K, int Kp, int dtype,
                long long gid_mul, long long gid_add, unsigned long long seed, float range, int threads);
 
+// Sparse checkpoints (hip/ckpt.hip: same definition): flags[r] = 1 when row r < rows differs, bitwise over
+// columns 0 .. K-1, from what init_rows wrote (v, w) or from a slot's initial bit pattern (sv_bits / sw_bits:
+// slot 0, slot 1; null slots are skipped).  fp32 and bf16 tables.  Returns the number of flagged rows;
+// changed_rows_emit then lists them in ascending order.
+long long changed_rows(const void* v, long long v_stride, const float* w, long long w_stride, const float* s0v,
+                       const float* s1v, long long s_stride, const float* s0w, const float* s1w, long long rows,
+                       int K, int dtype, long long gid_mul, long long gid_add, unsigned long long seed, float range,
+                       const uint32_t* sv_bits, const uint32_t* sw_bits, uint8_t* flags, int threads);
+void changed_rows_emit(const uint8_t* flags, long long rows, long long* out);
+
 }  // namespace cpu
 }  // namespace fm

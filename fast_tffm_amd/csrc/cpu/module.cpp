@@ -405,6 +405,30 @@ PYBIND11_MODULE(_fm_cpu, m) {
       py::arg("threads") = 0);
 
   m.def(
+      "changed_rows",  // flags + count; changed_rows_emit lists the flagged rows
+      [](u64 v, long long v_stride, u64 w, long long w_stride, u64 s0v, u64 s1v, long long s_stride, u64 s0w, u64 s1w,
+         long long rows, int K, int dtype, long long gid_mul, long long gid_add, unsigned long long seed, float range,
+         unsigned sv0, unsigned sv1, unsigned sw0, unsigned sw1, u64 flags, int threads) {
+        if (dtype != 0 && dtype != 1) throw std::invalid_argument("changed_rows: fp32 and bf16 tables");
+        const uint32_t sv[2] = {sv0, sv1}, sw[2] = {sw0, sw1};
+        py::gil_scoped_release nogil;
+        return fm::cpu::changed_rows(P<const void>(v), v_stride, P<const float>(w), w_stride, P<const float>(s0v),
+                                     P<const float>(s1v), s_stride, P<const float>(s0w), P<const float>(s1w), rows, K,
+                                     dtype, gid_mul, gid_add, seed, range, sv, sw, P<uint8_t>(flags), threads);
+      },
+      py::arg("v"), py::arg("v_stride"), py::arg("w"), py::arg("w_stride"), py::arg("s0v"), py::arg("s1v"),
+      py::arg("s_stride"), py::arg("s0w"), py::arg("s1w"), py::arg("rows"), py::arg("K"), py::arg("dtype"),
+      py::arg("gid_mul"), py::arg("gid_add"), py::arg("seed"), py::arg("range"), py::arg("sv0"), py::arg("sv1"),
+      py::arg("sw0"), py::arg("sw1"), py::arg("flags"), py::arg("threads") = 0);
+  m.def(
+      "changed_rows_emit",
+      [](u64 flags, long long rows, u64 out) {
+        py::gil_scoped_release nogil;
+        fm::cpu::changed_rows_emit(P<const uint8_t>(flags), rows, P<long long>(out));
+      },
+      py::arg("flags"), py::arg("rows"), py::arg("out"));
+
+  m.def(
       "csr_rows",
       [](int B, u64 offsets, u64 ex_of_occ) { fm::cpu::csr_rows(B, P<const int>(offsets), P<int>(ex_of_occ)); },
       py::arg("B"), py::arg("offsets"), py::arg("ex_of_occ"));

@@ -27,6 +27,7 @@ using u64 = std::uintptr_t;
 #include "auc.hip"
 #include "shard.hip"
 #include "init.hip"
+#include "ckpt.hip"
 #include "parse.hip"
 #include "batch_gather.hip"
 #include "feeder.hip"
@@ -384,6 +385,33 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       py::arg("v"), py::arg("v_stride"), py::arg("w"), py::arg("w_stride"), py::arg("rows"), py::arg("Kp"),
       py::arg("stream"), py::arg("idx") = 0);
   m.attr("FP8_NORM_COL") = fm::kFp8Norm;
+
+  m.attr("CKPT_TILE") = fm::kCkTile;
+  m.def("changed_workspace_bytes", &fm::changed_workspace_bytes, py::arg("rows"));
+  m.def("changed_total_offset", &fm::changed_total_offset, py::arg("rows"));
+  m.def(
+      "changed_scan",  // flags + tile offsets; the 64-bit total lands at ws + changed_total_offset(rows)
+      [](u64 v, long long v_stride, u64 w, long long w_stride, u64 s0v, u64 s1v, long long s_stride, u64 s0w, u64 s1w,
+         long long rows, int K, int Kp, int dtype, long long gid_mul, long long gid_add, unsigned long long seed,
+         float range, unsigned sv0, unsigned sv1, unsigned sw0, unsigned sw1, u64 ws, size_t ws_bytes, u64 stream) {
+        fm::ChangedArgs a{};
+        a.v = P<const void>(v); a.v_stride = v_stride; a.w = P<const float>(w); a.w_stride = w_stride;
+        a.s0v = P<const void>(s0v); a.s1v = P<const void>(s1v); a.s_stride = s_stride;
+        a.s0w = P<const float>(s0w); a.s1w = P<const float>(s1w); a.rows = rows; a.K = K; a.Kp = Kp;
+        a.gid_mul = gid_mul; a.gid_add = gid_add; a.seed = seed; a.range = range;
+        a.sv_bits[0] = sv0; a.sv_bits[1] = sv1; a.sw_bits[0] = sw0; a.sw_bits[1] = sw1;
+        check(fm::launch_changed_scan(a, dtype, P<void>(ws), ws_bytes, S(stream)), "changed_scan");
+      },
+      py::arg("v"), py::arg("v_stride"), py::arg("w"), py::arg("w_stride"), py::arg("s0v"), py::arg("s1v"),
+      py::arg("s_stride"), py::arg("s0w"), py::arg("s1w"), py::arg("rows"), py::arg("K"), py::arg("Kp"),
+      py::arg("dtype"), py::arg("gid_mul"), py::arg("gid_add"), py::arg("seed"), py::arg("range"), py::arg("sv0"),
+      py::arg("sv1"), py::arg("sw0"), py::arg("sw1"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
+  m.def(
+      "changed_emit",
+      [](long long rows, u64 ws, u64 out, u64 stream) {
+        check(fm::launch_changed_emit(rows, P<void>(ws), P<long long>(out), S(stream)), "changed_emit");
+      },
+      py::arg("rows"), py::arg("ws"), py::arg("out"), py::arg("stream"));
 
   m.def(
       "owner_counts",

@@ -60,6 +60,7 @@ class FMTable:
         self.rows = max(1, -(-self.real_rows // m) * m)
         self.init_range = float(init_range)
         self.seed = int(seed)
+        self.init_seed = self.seed  # what the last reinit used (with init_range): sparse checkpoints compare against it
         dev = self.device
         self.fp8 = dtype == K.FP8
         if self.fp8 and self.device.type != "cuda":
@@ -100,9 +101,14 @@ class FMTable:
     def state(self) -> K.TableState:
         return K.TableState(self.v, self.w, self.s0v, self.s1v, self.s0w, self.s1w)
 
-    def reinit(self, seed: int | None = None) -> None:
-        """U(-r, r) over w and v[:K] as a pure function of (seed, global id, column)."""
+    def reinit(self, seed: int | None = None, init_range: float | None = None) -> None:
+        """U(-r, r) over w and v[:K] as a pure function of (seed, global id, column).  The seed and range
+        used are recorded (``init_seed``, ``init_range``): ``changed_rows`` and sparse checkpoints regenerate
+        untouched rows from them."""
         seed = self.seed if seed is None else int(seed)
+        if init_range is not None:
+            self.init_range = float(init_range)
+        self.init_seed = seed
         args = dict(v=self.v.data_ptr(), v_stride=self.v.stride(0), w=self.w.data_ptr(), w_stride=self.w.stride(0),
                     rows=self.rows, K=self.K, Kp=self.Kp, dtype=K.dtype_code(self.dtype), gid_mul=self.world,
                     gid_add=self.rank, seed=seed & 0xFFFFFFFFFFFFFFFF, range=self.init_range)
@@ -111,6 +117,21 @@ class FMTable:
         else:
             native.cpu().init_rows(**args)
         self._zero_dead_rows()
+
+    def reset_slots(self, slot_init=None) -> None:
+        """Optimizer slots back to their initial constants (``slot_init``: [slot 0, slot 1] values, default
+        this table's optimizer's)."""
+        s0, s1 = K.slot_init_values(self.opt) if slot_init is None else (float(slot_init[0]), float(slot_init[1]))
+        self.s0v.fill_(s0)
+        self.s0w.fill_(s0)
+        if self.s1v is not None:
+            self.s1v.fill_(s1)
+            self.s1w.fill_(s1)
+
+    def changed_rows(self) -> torch.Tensor:
+        """Ascending local rows (int64, on the table's device) that differ bit for bit from their initial
+        state -- what the last ``reinit`` wrote and the slots' initial constants (``ops.kernels.changed_rows``)."""
+        return K.changed_rows(self)
 
     def _zero_dead_rows(self) -> None:
         # the last shard may own fewer real ids than allocated rows (rows >= 1, rows_multiple)

@@ -860,6 +860,74 @@ def auc(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None
 
 
 # ---------------------------------------------------------------------------
+# sparse checkpoints: rows that differ from their initial state
+# ---------------------------------------------------------------------------
+def _bits_of(value: float, dtype: torch.dtype) -> int:
+    """The bit pattern torch stores for ``value`` in ``dtype`` (what ``torch.full`` wrote), as an int."""
+    t = torch.full((1,), value, dtype=dtype)
+    return int(t.view(torch.int16 if dtype == torch.bfloat16 else torch.int32).item()) & (
+        0xFFFF if dtype == torch.bfloat16 else 0xFFFFFFFF)
+
+
+def slot_init_values(opt: OptConfig) -> tuple[float, float]:
+    """Initial values of optimizer slot 0 and slot 1 of a table with ``opt`` (models/table.py)."""
+    return (float(opt.initial_accumulator) if opt.name in ("adagrad", "ftrl") else 0.0, 0.0)
+
+
+def changed_rows(table, *, seed: int | None = None) -> torch.Tensor:
+    """Ascending local rows (int64, on ``table.device``) of an ``FMTable`` shard that differ, bit for bit
+    over columns ``0 .. K-1``, from their initial state: ``v`` / ``w`` from what ``init_rows`` writes for
+    (``seed``, ``table.init_range``) -- fp8: the stored bytes and the row scale; the norm word is derived
+    and ignored --, the optimizer slots from the constants they start from.  Only rows with a real global
+    id (``< vocab_size``) are looked at.  ``seed``: the init seed to compare against (default: the one the
+    table recorded, ``table.init_seed``).
+
+    GPU: hip/ckpt.hip on the current stream -- one pass over the table, a bitmap, an ordered compaction;
+    one host read (the count).  CPU: the same definition (cpu/kernels.cpp), fp32 and bf16 tables."""
+    dev = table.device
+    seed = int(table.init_seed if seed is None else seed) & 0xFFFFFFFFFFFFFFFF
+    rows = min(table.rows, table.real_rows)
+    _check(rows <= 2**31, "changed_rows: at most 2^31 rows per shard")
+    s0, s1 = slot_init_values(table.opt)
+    sdt = table.state_dtype
+    sv0, sv1 = _bits_of(s0, sdt), _bits_of(s1, sdt)
+    sw0, sw1 = _bits_of(s0, torch.float32), _bits_of(s1, torch.float32)
+    v, w = table.v, table.wx if table.fp8 else table.w
+    v_stride = _chk_rows(v, table.Kp, "v")
+    for name in ("s0v", "s1v"):
+        t = getattr(table, name)
+        if t is not None:
+            _check(t.dtype == sdt and t.stride(1) == 1 and t.stride(0) == table.s0v.stride(0)
+                   and t.data_ptr() % 16 == 0 and t.stride(0) % 4 == 0, f"{name}: state rows of {sdt}, 16-byte aligned")
+    for name in ("w", "s0w", "s1w"):
+        t = getattr(table, name)
+        _check(t is None or t.dtype == torch.float32, f"{name}: fp32")
+    common = dict(v=_p(v), v_stride=v_stride, w=_p(w), w_stride=w.stride(0), s0v=_p(table.s0v), s1v=_p(table.s1v),
+                  s_stride=table.s0v.stride(0), s0w=_p(table.s0w), s1w=_p(table.s1w), rows=rows, K=table.K,
+                  dtype=dtype_code(table.dtype), gid_mul=table.world, gid_add=table.rank, seed=seed,
+                  range=float(table.init_range), sv0=sv0, sv1=sv1, sw0=sw0, sw1=sw1)
+    if dev.type == "cuda":
+        h = native.hip()
+        need = int(h.changed_workspace_bytes(rows))
+        ws = torch.empty((need + 7) // 8, dtype=torch.int64, device=dev)
+        st = _stream(v)
+        h.changed_scan(**common, Kp=table.Kp, ws=_p(ws), ws_bytes=ws.numel() * 8, stream=st)
+        n = int(ws[int(h.changed_total_offset(rows)) // 8].item())  # the one host read
+        out = torch.empty(n, dtype=torch.int64, device=dev)
+        if n:
+            h.changed_emit(rows=rows, ws=_p(ws), out=_p(out), stream=st)
+        return out
+    _check(not table.fp8, "changed_rows: fp8 tables run on the GPU kernels only")
+    c = native.cpu()
+    flags = torch.empty(max(rows, 1), dtype=torch.uint8)
+    n = int(c.changed_rows(**common, flags=_p(flags)))
+    out = torch.empty(n, dtype=torch.int64)
+    if n:
+        c.changed_rows_emit(flags=_p(flags), rows=rows, out=_p(out))
+    return out
+
+
+# ---------------------------------------------------------------------------
 # row-sharded helpers
 # ---------------------------------------------------------------------------
 def gather_rows(req: torch.Tensor, table: TableState, Kp: int, out: torch.Tensor, threads: int = 0,

@@ -116,7 +116,8 @@ class Trainer:
         rs = {"epoch": self.reader_state.epoch, "batches_in_epoch": self.reader_state.batches_in_epoch,
               "draw_version": DRAW_VERSION}
         return ckpt.save_checkpoint(self.model, self.cfg.log_dir, self.model.global_step, reader_state=rs,
-                                    ctx=self.ctx if self.world > 1 else None)
+                                    ctx=self.ctx if self.world > 1 else None,
+                                    table_format=getattr(self.cfg, "checkpoint_format", "dense"))
 
     def _all_have_batch(self, have: bool) -> bool:
         if self.world == 1:

@@ -14,6 +14,13 @@ Layout here (one directory per step, one file per table shard)::
         w [rows] fp32, v [rows, K] (table dtype), s0w/s0v (Adagrad acc / FTRL n),
         s1w/s1v (FTRL z); local row r of shard s holds global id r * W + s.
 
+``table_format="sparse"`` (``[Train] checkpoint_format = sparse``): the shard file holds ``rows``
+[n] int64 -- the ascending local rows that differ, bit for bit, from their initial state
+(``FMTable.changed_rows``: table init is a pure function of (seed, global id, column), the slots start
+from constants) -- and the per-row tensors with one entry per listed row; ``meta.json`` records
+``table_format``, ``init_seed``, ``init_range`` and ``slot_init``.  Restore re-initialises the table from
+those and scatters the saved rows; the offline readers regenerate dense chunks on the host.
+
 Every rank writes only its own shard (replicated modes: rank 0 writes the
 single table); rank 0 writes meta.json and the index after a barrier, so the
 index never points at a partial checkpoint.  Restore re-shards on the fly when
@@ -67,22 +74,30 @@ _ST_DTYPE = {torch.float32: "F32", torch.bfloat16: "BF16", torch.uint8: "U8", to
 CHUNK_BYTES = 256 << 20   # rows move device -> file (and back) in chunks of about this size
 
 
-def _table_sources(table) -> dict:
+def _table_sources(table, index: torch.Tensor | None = None) -> dict:
     """name -> (dtype, shape, chunk(r0, r1) -> tensor of rows [r0, r1)) of a table shard.
 
     Chunked so that a checkpoint of a 125M-row shard never holds more than one chunk of
-    any table tensor in host memory (nor a full-size dequantised copy on the device)."""
-    K, n = table.K, table.saved_rows
+    any table tensor in host memory (nor a full-size dequantised copy on the device).
+    ``index`` (int64, on the table's device): the sparse form -- entry i of every tensor is local row
+    ``index[i]``, and ``rows`` holds the index itself."""
+    K = table.K
+    n = table.saved_rows if index is None else int(index.numel())
+
+    def sel(r0, r1):
+        return slice(r0, r1) if index is None else index[r0:r1]
 
     def rows(t, cols=None):
-        return lambda r0, r1: (t[r0:r1] if cols is None else t[r0:r1, :cols])
+        return lambda r0, r1: (t[sel(r0, r1)] if cols is None else t[sel(r0, r1), :cols])
 
-    src = {"w": (torch.float32, (n,), rows(table.w)),
+    src = {} if index is None else {"rows": (torch.int64, (n,), lambda r0, r1: index[r0:r1])}
+    src.update({
+           "w": (torch.float32, (n,), rows(table.w)),
            "v": (table.dtype if not table.fp8 else torch.float32, (n, K),
-                 (lambda r0, r1: table.dense_v(slice(r0, r1))[:, :K])
+                 (lambda r0, r1: table.dense_v(sel(r0, r1))[:, :K])
                  if table.fp8 else rows(table.v, K)),
            "s0w": (torch.float32, (n,), rows(table.s0w)),
-           "s0v": (torch.float32, (n, K), rows(table.s0v, K))}
+           "s0v": (torch.float32, (n, K), rows(table.s0v, K))})
     if table.fp8:  # exact fp8 payload + scales next to the portable fp32 values
         src["v_fp8"] = (torch.uint8, (n, table.Kp), rows(table.v.view(torch.uint8)))
         src["v_scale"] = (torch.float32, (n,), rows(table.scale))
@@ -124,9 +139,16 @@ def _table_tensors(table) -> dict[str, torch.Tensor]:
     return {k: c(0, shape[0]).detach().to(dt).cpu().contiguous() for k, (dt, shape, c) in _table_sources(table).items()}
 
 
+TABLE_FORMATS = ("dense", "sparse")
+
+
 def save_checkpoint(model, log_dir: str, step: int, *, reader_state: dict | None = None, ctx=None,
-                    max_to_keep: int = 5) -> str:
-    """Write a checkpoint of ``model`` (a FactorizationMachine) at ``step``; returns its directory."""
+                    max_to_keep: int = 5, table_format: str = "dense") -> str:
+    """Write a checkpoint of ``model`` (a FactorizationMachine) at ``step``; returns its directory.
+    ``table_format``: ``dense`` (every row) or ``sparse`` (the rows that differ from their init)."""
+    if table_format not in TABLE_FORMATS:
+        raise ValueError(f"table_format must be dense or sparse, got {table_format!r}")
+    sparse = table_format == "sparse"
     table = model.table
     rank = ctx.rank if ctx is not None else 0
     world = ctx.world if ctx is not None else 1
@@ -139,12 +161,15 @@ def save_checkpoint(model, log_dir: str, step: int, *, reader_state: dict | None
     if sharded or rank == 0:
         shard_rank, shard_world = (table.rank, table.world)
         tmp = os.path.join(path, _shard_name(shard_rank, shard_world) + ".tmp")
-        sources = _table_sources(table)
+        sources = _table_sources(table, table.changed_rows() if sparse else None)
         if getattr(model, "gbias", None) is not None:  # replicated global bias + optimizer state
             for k in ("gbias", "gbias_s0", "gbias_s1"):
                 t = getattr(model, k)
                 sources[k] = (torch.float32, tuple(t.shape), (lambda t_: lambda r0, r1: t_[r0:r1])(t))
-        write_safetensors_streamed(tmp, sources, {"format": FORMAT, "rank": shard_rank, "world": shard_world})
+        fmeta = {"format": FORMAT, "rank": shard_rank, "world": shard_world}
+        if sparse:
+            fmeta["table_format"] = "sparse"
+        write_safetensors_streamed(tmp, sources, fmeta)
         os.replace(tmp, os.path.join(path, _shard_name(shard_rank, shard_world)))
     # every rank reads its own file subset (reader.py / loader.cpp shard the files by rank),
     # so each rank's reader position is saved and restored separately
@@ -172,6 +197,11 @@ def save_checkpoint(model, log_dir: str, step: int, *, reader_state: dict | None
             "reader_world": world,
             "global_bias": float(model.gbias.item()) if getattr(model, "gbias", None) is not None else None,
         }
+        if sparse:  # what restore regenerates the unlisted rows from
+            from ..ops.kernels import slot_init_values
+
+            meta.update(table_format="sparse", init_seed=int(table.init_seed), init_range=float(table.init_range),
+                        slot_init=list(slot_init_values(table.opt)))
         with open(os.path.join(path, "meta.json.tmp"), "w") as f:
             json.dump(meta, f, indent=1)
         os.replace(os.path.join(path, "meta.json.tmp"), os.path.join(path, "meta.json"))
@@ -226,7 +256,10 @@ def restore_checkpoint(model, ckpt_dir: str) -> dict:
                 for k in ("gbias", "gbias_s0", "gbias_s1"):
                     if k in f.keys():
                         getattr(model, k).copy_(f.get_tensor(k).to(getattr(model, k).device))
-    if os.path.exists(direct):
+    first = next(iter(_iter_shards(ckpt_dir)), None)
+    if meta.get("table_format") == "sparse" or (first is not None and _is_sparse_file(first[2])):
+        _restore_sparse(table, ckpt_dir, meta, direct, K, dev)
+    elif os.path.exists(direct):
         for r0, t in _iter_row_chunks(direct):
             n = t["w"].shape[0]
             _copy_rows(table, slice(r0, r0 + n), t, K, dev)
@@ -250,10 +283,108 @@ def restore_checkpoint(model, ckpt_dir: str) -> dict:
 _ROW_KEYS = ("w", "v", "s0w", "s0v", "s1w", "s1v", "v_fp8", "v_scale")
 
 
-def _iter_row_chunks(path: str):
-    """(first row, {name: rows}) chunks of a shard file's per-row tensors, read lazily."""
+def _is_sparse_file(path: str) -> bool:
+    with safe_open(path, framework="pt") as f:
+        return "rows" in f.keys()
+
+
+def _sparse_init(meta: dict) -> tuple[int, float, list]:
+    try:
+        return int(meta["init_seed"]), float(meta["init_range"]), [float(x) for x in meta["slot_init"]]
+    except KeyError as e:
+        raise ValueError(f"sparse checkpoint without {e.args[0]} in meta.json: its unlisted rows cannot be "
+                         "regenerated") from None
+
+
+def _restore_sparse(table, ckpt_dir: str, meta: dict, direct: str, K: int, dev) -> None:
+    """Sparse restore: the table's init from the checkpoint's seed and range (not the config's), the slots'
+    initial constants, then the saved rows on top -- of this rank's own file, or, re-sharding, of every
+    file's rows whose global id this rank owns."""
+    seed, rng, slot_init = _sparse_init(meta)
+    table.reinit(seed=seed, init_range=rng)
+    table.reset_slots(slot_init)
+    if os.path.exists(direct):
+        for rows, t in _iter_sparse_chunks(direct):
+            _copy_rows(table, rows.to(dev), t, K, dev)
+        return
+    for s_rank, s_world, path in _iter_shards(ckpt_dir):
+        for rows, t in _iter_sparse_chunks(path):
+            gid = rows * s_world + s_rank
+            mine = (gid % table.world == table.rank) & (gid < table.vocab_size)
+            if not bool(mine.any()):
+                continue
+            sel = torch.nonzero(mine).flatten()
+            local = torch.div(gid[sel], table.world, rounding_mode="floor")
+            _copy_rows(table, local.to(dev), {k: v[sel] for k, v in t.items()}, K, dev)
+
+
+def _iter_sparse_chunks(path: str):
+    """(local rows [m] int64, {name: their entries}) chunks of a sparse shard file, read lazily."""
     with safe_open(path, framework="pt") as f:
         keys = [k for k in f.keys() if k in _ROW_KEYS]
+        n = f.get_slice("rows").get_shape()[0]
+        row_bytes = 8 + sum(4 * int(np.prod(f.get_slice(k).get_shape()[1:] or [1])) for k in keys)
+        step = max(1, CHUNK_BYTES // row_bytes)
+        for r0 in range(0, n, step):
+            r1 = min(n, r0 + step)
+            yield f.get_slice("rows")[r0:r1], {k: f.get_slice(k)[r0:r1] for k in keys}
+
+
+_META_DTYPES = {"float32": torch.float32, "bfloat16": torch.bfloat16}
+
+
+def _iter_sparse_as_dense(path: str, f, keys: list):
+    """The dense chunks of a sparse shard file (the offline readers' view): every chunk's init regenerated
+    on the host (the CPU twin of the table init), the slots filled with their initial constants, the saved
+    rows that fall in the chunk laid over them.  fp32 and bf16 tables: there is no host twin of the fp8 init."""
+    from ..models.table import shard_rows
+    from ..ops import native
+    from ..ops.kernels import dtype_code, padded_k
+
+    meta = read_meta(os.path.dirname(path))
+    m = re.search(r"shard-(\d+)-of-(\d+)\.safetensors$", path)
+    s_rank, s_world = int(m.group(1)), int(m.group(2))
+    dtype = _META_DTYPES.get(meta["dtype"])
+    if dtype is None or "v_fp8" in keys:
+        raise ValueError(f"{path}: a sparse checkpoint of an fp8 table cannot be read offline (its untouched "
+                         "rows are regenerated by the GPU init, which has no host twin); restore it on the GPU, "
+                         "or train with checkpoint_format = dense")
+    seed, rng, slot_init = _sparse_init(meta)
+    V, K = int(meta["vocabulary_size"]), int(meta["factor_num"])
+    Kp = padded_k(K, dtype)
+    n = shard_rows(V, s_world, s_rank)
+    rows = f.get_slice("rows")[:]  # (8 bytes per saved row; the values stay on disk until their chunk)
+    row_bytes = sum(4 * int(np.prod(f.get_slice(k).get_shape()[1:] or [1])) for k in keys)
+    step = max(1, CHUNK_BYTES // max(row_bytes, 1))
+    cpu = native.cpu()
+    for r0 in range(0, n, step):
+        r1 = min(n, r0 + step)
+        v = torch.zeros((r1 - r0, Kp), dtype=dtype)
+        w = torch.zeros(r1 - r0, dtype=torch.float32)
+        cpu.init_rows(v=v.data_ptr(), v_stride=Kp, w=w.data_ptr(), w_stride=1, rows=r1 - r0, K=K, Kp=Kp,
+                      dtype=dtype_code(dtype), gid_mul=s_world, gid_add=r0 * s_world + s_rank,
+                      seed=seed & 0xFFFFFFFFFFFFFFFF, range=rng)
+        t = {"w": w, "v": v[:, :K].contiguous()}
+        for slot, init in zip(("s0", "s1"), slot_init):
+            if slot + "w" in keys:
+                t[slot + "w"] = torch.full((r1 - r0,), init, dtype=torch.float32)
+                t[slot + "v"] = torch.full((r1 - r0, K), init, dtype=torch.float32)
+        lo, hi = (int(x) for x in torch.searchsorted(rows, torch.tensor([r0, r1], dtype=torch.int64)))
+        if hi > lo:
+            at = rows[lo:hi] - r0
+            for k in keys:
+                t[k][at] = f.get_slice(k)[lo:hi].to(t[k].dtype)
+        yield r0, t
+
+
+def _iter_row_chunks(path: str):
+    """(first row, {name: rows}) chunks of a shard file's per-row tensors, read lazily.  A sparse file
+    yields the dense chunks a dense file of the same table would (``_iter_sparse_as_dense``)."""
+    with safe_open(path, framework="pt") as f:
+        keys = [k for k in f.keys() if k in _ROW_KEYS]
+        if "rows" in f.keys():
+            yield from _iter_sparse_as_dense(path, f, keys)
+            return
         n = f.get_slice("w").get_shape()[0]
         row_bytes = sum(4 * int(np.prod(f.get_slice(k).get_shape()[1:] or [1])) for k in keys)
         step = max(1, CHUNK_BYTES // max(row_bytes, 1))
