@@ -1,11 +1,13 @@
-"""Command line: ``python run.py {train,predict,generate,convert,import_tf,export_tf} CONFIG [options]``.
+"""Command line: ``python run.py {train,predict,explain,generate,convert,import_tf,export_tf} CONFIG [options]``.
 
 Same arguments as the reference's run_tffm.py (run_tffm.py:124-162):
   task {train,predict,generate}, config_file,
   --dist JOB_NAME TASK_INDEX PS_HOSTS WORKER_HOSTS, --protocol, --wait-for-workers N,
   -t/--trace FILE, -m/--monitor, --export_path DIR.
 Extensions: --device {auto,cpu,cuda}, --mode {auto,local,shard,dp,dp_dense},
---max-steps N, --log-dir DIR (overrides [General] log_dir), and the task
+--max-steps N, --log-dir DIR (overrides [General] log_dir), the task ``explain CONFIG [--top N]``
+(exact per-feature attributions of the predict files' scores: ``<file>_contrib`` and
+``<file>_importance``, trainer.Trainer.explain; the reference has no equivalent), and the task
 ``convert CONFIG --out DIR``: parse the config's train files (+ weight files) once
 into binary CSR caches (``DIR/<name>.fmb``, data/bincache.py) that ``train``
 reads at memory speed when ``train_files`` points at them.  Checkpoint migration:
@@ -31,7 +33,7 @@ import sys
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="run.py", description="MI355X-native distributed factorization machine")
-    p.add_argument("task", choices=["train", "predict", "generate", "convert", "import_tf", "export_tf"])
+    p.add_argument("task", choices=["train", "predict", "explain", "generate", "convert", "import_tf", "export_tf"])
     p.add_argument("config_file", type=str)
     p.add_argument("--dist", nargs=4, metavar=("JOB_NAME", "TASK_INDEX", "PS_HOSTS", "WORKER_HOSTS"), default=None,
                    help="For distributed training or prediction")
@@ -48,6 +50,8 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--max-steps", type=int, default=None)
     p.add_argument("--log-dir", default=None)
     p.add_argument("--out", default=None, help="convert: output directory of the .fmb caches")
+    p.add_argument("--top", type=int, default=None, metavar="N",
+                   help="explain: keep only the N largest |contribution| tokens of every line")
     p.add_argument("--tf_checkpoint", default=None,
                    help="import_tf: TF checkpoint directory (its 'checkpoint' file names the newest) or prefix")
     return p
@@ -78,7 +82,7 @@ def main(argv: list[str] | None = None) -> int:
         # queues (HIP's default 4 makes them share and serialize); before HIP starts
         fmdist.ensure_hw_queues()
 
-    if args.task == "predict" and cfg.log_dir is None:
+    if args.task in ("predict", "explain") and cfg.log_dir is None:
         print("Missing log directory. Must include a checkpoint file.")
         os._exit(1)
     if args.task == "generate":
@@ -130,6 +134,8 @@ def main(argv: list[str] | None = None) -> int:
     try:
         if args.task == "train":
             tr.train()
+        elif args.task == "explain":
+            tr.explain(top=args.top)
         else:
             tr.predict()
     finally:

@@ -142,6 +142,40 @@ FwdResult fwd(int B, const int* offsets, const int* rows, const float* vals, con
   return FwdResult{loss_sum, regv_sum, regw_sum};
 }
 
+void explain(int B, const int* offsets, const int* rows, const float* vals, const void* v, long long v_stride,
+             const float* w, long long w_stride, int Kp, int dtype, const float* bias, float* contrib, float* pred,
+             int threads) {
+  set_threads(threads);
+#pragma omp parallel
+  {
+    std::vector<float> S(Kp), row(Kp);
+#pragma omp for schedule(static)
+    for (int i = 0; i < B; ++i) {
+      std::fill(S.begin(), S.end(), 0.f);
+      for (int j = offsets[i]; j < offsets[i + 1]; ++j) {
+        const float x = vals ? vals[j] : 1.f;
+        load_row(v, (long long)rows[j] * v_stride, Kp, dtype, row.data());
+        for (int k = 0; k < Kp; ++k) S[k] += x * row[k];
+      }
+      float total = 0.f;
+      for (int j = offsets[i]; j < offsets[i + 1]; ++j) {
+        const long long r = rows[j];
+        const float x = vals ? vals[j] : 1.f;
+        load_row(v, r * v_stride, Kp, dtype, row.data());
+        float d = 0.f;
+        for (int k = 0; k < Kp; ++k) {
+          const float xv = x * row[k];
+          d += xv * (S[k] - xv);
+        }
+        const float c = x * w[r * w_stride] + 0.5f * d;
+        contrib[j] = c;
+        total += c;
+      }
+      pred[i] = total + (bias ? bias[0] : 0.f);
+    }
+  }
+}
+
 int dedup(int n, const uint32_t* keys, uint32_t* skeys, int* perm, uint32_t* uniq, int* seg_start, int* inv,
           const int* ex_of_occ, int* sorted_ex, const float* vals, float* sorted_x) {
   if (n <= 0) {

@@ -24,6 +24,12 @@ FwdResult fwd(int B, const int* offsets, const int* rows, const float* vals, con
               int loss_type, float grad_scale, float* pred, float* r1, float* dpred, int threads,
               const float* bias = nullptr);
 
+// Exact per-occurrence attributions of the score (hip/fm_explain.hip: same definition):
+// contrib[j] = x_j w_j + 1/2 sum_f x_j v_jf (S_f - x_j v_jf); pred[i] = sum of example i's contributions + bias.
+void explain(int B, const int* offsets, const int* rows, const float* vals, const void* v, long long v_stride,
+             const float* w, long long w_stride, int Kp, int dtype, const float* bias, float* contrib, float* pred,
+             int threads);
+
 // Stable sort of (key, occurrence) + run-length encoding. Returns U.
 int dedup(int n, const uint32_t* keys, uint32_t* skeys, int* perm, uint32_t* uniq, int* seg_start, int* inv,
           const int* ex_of_occ, int* sorted_ex, const float* vals, float* sorted_x);

@@ -334,6 +334,19 @@ PYBIND11_MODULE(_fm_cpu, m) {
       py::arg("threads"), py::arg("bias") = 0);
 
   m.def(
+      "explain",
+      [](int B, u64 offsets, u64 rows, u64 vals, u64 v, long long v_stride, u64 w, long long w_stride, int Kp,
+         int dtype, u64 bias, u64 contrib, u64 pred, int threads) {
+        py::gil_scoped_release nogil;
+        fm::cpu::explain(B, P<const int>(offsets), P<const int>(rows), P<const float>(vals), P<const void>(v),
+                         v_stride, P<const float>(w), w_stride, Kp, dtype, P<const float>(bias), P<float>(contrib),
+                         P<float>(pred), threads);
+      },
+      py::arg("B"), py::arg("offsets"), py::arg("rows"), py::arg("vals"), py::arg("v"), py::arg("v_stride"),
+      py::arg("w"), py::arg("w_stride"), py::arg("Kp"), py::arg("dtype"), py::arg("bias"), py::arg("contrib"),
+      py::arg("pred"), py::arg("threads"));
+
+  m.def(
       "dedup",
       [](int n, u64 keys, u64 skeys, u64 perm, u64 uniq, u64 seg_start, u64 inv, u64 ex_of_occ, u64 sorted_ex,
          u64 vals, u64 sorted_x) {

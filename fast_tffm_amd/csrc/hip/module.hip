@@ -23,6 +23,7 @@ using u64 = std::uintptr_t;
 // Unity build: all kernel sources are compiled in this translation unit.
 #include "fm_bwd.hip"
 #include "fm_fwd.hip"
+#include "fm_explain.hip"
 #include "dedup.hip"
 #include "auc.hip"
 #include "shard.hip"
@@ -122,6 +123,31 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       py::arg("loss_partial"), py::arg("reg_partial"), py::arg("grid"), py::arg("stream"), py::arg("bias") = 0,
       py::arg("self_rows") = std::vector<long long>{}, py::arg("seg_idx") = 0, py::arg("seg_keys") = 0,
       py::arg("seg_shift") = 0, py::arg("max_feats") = -1);
+
+  m.def(
+      "explain",  // exact per-occurrence attributions (fm_explain.hip): contrib[nnz], pred[B] = sum + bias
+      [](int B, u64 offsets, u64 rows, u64 vals, u64 v, long long v_stride, u64 w, long long w_stride, int Kp,
+         int dtype, u64 bias, u64 contrib, u64 pred, u64 stream) {
+        fm::ExplainArgs a{};
+        a.B = B; a.offsets = P<const int>(offsets); a.rows = P<const int>(rows); a.vals = P<const float>(vals);
+        a.v = P<const void>(v); a.v_stride = v_stride; a.w = P<const float>(w); a.w_stride = w_stride; a.Kp = Kp;
+        a.bias = P<const float>(bias); a.contrib = P<float>(contrib); a.pred = P<float>(pred);
+        check(fm::launch_explain(a, dtype, S(stream)), "fm_explain");
+      },
+      py::arg("B"), py::arg("offsets"), py::arg("rows"), py::arg("vals"), py::arg("v"), py::arg("v_stride"),
+      py::arg("w"), py::arg("w_stride"), py::arg("Kp"), py::arg("dtype"), py::arg("bias"), py::arg("contrib"),
+      py::arg("pred"), py::arg("stream"));
+  m.def(
+      "importance",  // count / sum |c| / sum c (fp64) of every dedup segment
+      [](int U, u64 contrib, u64 perm, u64 seg_start, u64 count, u64 sum_abs, u64 sum, u64 stream) {
+        fm::ImportanceArgs a{};
+        a.U = U; a.contrib = P<const float>(contrib); a.perm = P<const int>(perm);
+        a.seg_start = P<const int>(seg_start); a.count = P<int>(count); a.sum_abs = P<double>(sum_abs);
+        a.sum = P<double>(sum);
+        check(fm::launch_importance(a, S(stream)), "fm_importance");
+      },
+      py::arg("U"), py::arg("contrib"), py::arg("perm"), py::arg("seg_start"), py::arg("count"), py::arg("sum_abs"),
+      py::arg("sum"), py::arg("stream"));
 
   m.def(
       "seg_index",

@@ -663,6 +663,18 @@ class FactorizationMachine:
         """Raw scores (logits for logistic loss), like the reference's pred_ops (run_tffm.py:10-17)."""
         return self.forward(b).pred
 
+    @torch.no_grad()
+    def explain(self, b: Batch) -> tuple[torch.Tensor, torch.Tensor]:
+        """Exact per-occurrence attributions of the scores of ``b``: ``(contrib [nnz], pred [B])``, the
+        contributions of an example adding up to its score less the global bias (``K.fm_explain``).
+        Row-sharded models gather the batch's rows like ``forward`` (a collective: every rank calls)."""
+        if self.closed and self.mode != "local":
+            raise RuntimeError("explain on a closed multi-rank FactorizationMachine")
+        if self._exchange is not None:
+            return self._exchange.explain(b)
+        return K.fm_explain(b.offsets, b.ids.to(torch.int32), b.vals, self.table.v, self.table.w, self.Kp,
+                            bias=self.gbias, threads=self.cfg.threads)
+
     def eval_loss(self, b: Batch) -> float:
         """Weighted mean loss of the configured type (reference valid_op, fm_model.py:317-333)."""
         fo = self.forward(b, loss=self.cfg.loss_type)

@@ -305,6 +305,54 @@ def fm_forward(offsets: torch.Tensor, rows: torch.Tensor, vals: torch.Tensor | N
     return FwdOut(pred, r1, dpred if lt else None, loss_sum, regv, regw)
 
 
+def fm_explain(offsets: torch.Tensor, rows: torch.Tensor, vals: torch.Tensor | None, v: torch.Tensor,
+               w: torch.Tensor, Kp: int, *, bias: torch.Tensor | None = None, contrib: torch.Tensor | None = None,
+               pred: torch.Tensor | None = None, threads: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    """Exact attribution of every occurrence of a CSR batch (hip/fm_explain.hip; the reference has none).
+
+    c_j = x_j w_j + 1/2 sum_f x_j v_jf (S_f - x_j v_jf) with S_f = sum_j x_j v_jf over the example: each
+    pair's term split equally between its two occurrences, the Shapley value of the occurrence against the
+    empty example.  Returns ``(contrib [nnz], pred [B])`` with ``pred_i = sum_j c_j + bias`` -- ``fm_forward``'s
+    score up to rounding.  fp8 rows (GPU only): the dot product on the dequantised row, the self term from
+    the row's stored |v|^2, as the forward.  ``rows`` are plain row indices into ``v`` / ``w`` (table rows
+    or gathered wire rows)."""
+    dev = rows.device
+    B = offsets.numel() - 1
+    _chk_vec(offsets, torch.int32, B + 1, "offsets", dev)
+    nnz = rows.numel()
+    _chk_vec(rows, torch.int32, nnz, "rows", dev)
+    _chk_vec(vals, torch.float32, nnz, "vals", dev)
+    v_stride = _chk_rows(v, Kp, "v")
+    _check(v.device == dev, "v: expected the rows' device")
+    _check(w.dim() == 1 or (w.dim() == 2 and w.shape[1] == 1), "w: expected a vector (possibly strided)")
+    _check(w.dtype == torch.float32 and w.device == dev, "w: expected float32 on the rows' device")
+    w_stride = w.stride(0)
+    _check(w.shape[0] >= v.shape[0], "w: fewer rows than v")
+    _check(v.dtype != FP8 or w_stride >= 3, "fp8 rows: w must be a strided view of [w, scale, |v|^2, .] row tails")
+    _check(v.dtype != FP8 or (w_stride % 4 == 0 and w.data_ptr() % 16 == 0),
+           "fp8 rows: the [w, scale, |v|^2, .] tails must be 16-byte aligned")
+    _check(v_stride * v.element_size() < 2**32, "v: row stride must be below 4 GiB")
+    _check(nnz == 0 or v.shape[0] > 0, "rows index an empty table")
+    if bias is not None:
+        _chk_vec(bias, torch.float32, 1, "bias", dev)
+    _range_check(rows, v.shape[0], "rows")
+    if contrib is None:
+        contrib = torch.empty(nnz, dtype=torch.float32, device=dev)
+    if pred is None:
+        pred = torch.empty(B, dtype=torch.float32, device=dev)
+    _chk_vec(contrib, torch.float32, nnz, "contrib", dev)
+    _chk_vec(pred, torch.float32, B, "pred", dev)
+    dt = dtype_code(v.dtype)
+    kw = dict(B=B, offsets=_p(offsets), rows=_p(rows), vals=_p(vals), v=_p(v), v_stride=v_stride, w=_p(w),
+              w_stride=w_stride, Kp=Kp, dtype=dt, bias=_p(bias), contrib=_p(contrib), pred=_p(pred))
+    if _is_gpu(rows):
+        native.hip().explain(stream=_stream(rows), **kw)
+    else:
+        _check(v.dtype != FP8, "fp8 tables are a GPU path")
+        native.cpu().explain(threads=threads, **kw)
+    return contrib[:nnz], pred[:B]
+
+
 # ---------------------------------------------------------------------------
 # dedup
 # ---------------------------------------------------------------------------
@@ -563,6 +611,38 @@ def dedup(keys: torch.Tensor, *, ws: DedupWorkspace | None = None, key_bits: int
         ws.counts[0] = U
         out.U_host = U
     return out
+
+
+def feature_importance(contrib: torch.Tensor, dd: DedupOut) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor,
+                                                                     torch.Tensor]:
+    """Per-feature sums of ``fm_explain``'s contributions over a batch: ``(uniq, count, sum_abs, sum)`` for the
+    U distinct ids of ``dd``, a dedup of the batch's ids that kept the occurrence permutation
+    (``dedup(ids, want_perm=True)``).  Sums are fp64 in a fixed order (hip/fm_explain.hip: lane-strided
+    partial sums over the segment in sorted order, then a butterfly): bitwise repeatable.  Synchronises
+    for U."""
+    dev = contrib.device
+    _chk_vec(contrib, torch.float32, dd.n, "contrib", dev)
+    _check(dd.perm is not None and dd.sorted_ex is not dd.perm and dd.ex_shift == 0,
+           "feature_importance: the dedup must carry the occurrence permutation (want_perm=True)")
+    _check(dd.perm.device == dev, "contrib: expected the dedup's device")
+    U = dd.sync()
+    uniq = dd.uniq[:U]
+    count = torch.empty(U, dtype=torch.int32, device=dev)
+    sum_abs = torch.empty(U, dtype=torch.float64, device=dev)
+    total = torch.empty(U, dtype=torch.float64, device=dev)
+    if U == 0:
+        return uniq, count, sum_abs, total
+    if _is_gpu(contrib):
+        native.hip().importance(U=U, contrib=_p(contrib), perm=_p(dd.perm), seg_start=_p(dd.seg_start),
+                                count=_p(count), sum_abs=_p(sum_abs), sum=_p(total), stream=_stream(contrib))
+    else:
+        seg = dd.seg_start[: U + 1].long()
+        count.copy_(seg[1:] - seg[:-1])
+        c = contrib[dd.perm[: dd.n].long()].double()
+        which = torch.repeat_interleave(torch.arange(U), count.long())
+        sum_abs.zero_().index_add_(0, which, c.abs())
+        total.zero_().index_add_(0, which, c)
+    return uniq, count, sum_abs, total
 
 
 # ---------------------------------------------------------------------------

@@ -1206,6 +1206,24 @@ class ShardExchange(_Base):
             self.slots[pl.slot].done = done
         return out
 
+    @torch.no_grad()
+    def explain(self, b: Batch) -> tuple[torch.Tensor, torch.Tensor]:
+        """``forward``'s gather, then the attributions over the wire rows: the eval plan's inverse map is
+        each occurrence's row in the gathered buffer (plain row indices, no segment lookup, no self rows)."""
+        self.flush()
+        self.m.ws.ensure(b.B, b.nnz)
+        pl = self._take_plan(b, False)
+        part = pl.parts[0]
+        buf, work = self._gather_part(pl, part, async_op=False)
+        src_v, src_w = self.wire.views(buf)
+        out = K.fm_explain(b.offsets, part.dd.inv[: b.nnz], b.vals, src_v, src_w, self.Kp, bias=self.m.gbias,
+                           threads=self.m.cfg.threads)
+        if self.dev.type == "cuda":
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(self.dev))
+            self.slots[pl.slot].done = done
+        return out
+
 
 class DPExchange(_Base):
     """Replicated table; sparse all-gather of (ids, gradient rows)."""
@@ -1265,6 +1283,12 @@ class DPExchange(_Base):
         return K.fm_forward(b.offsets, b.ids.to(torch.int32), b.vals, t.v, t.w, self.Kp, labels=b.labels,
                             weights=b.weights, loss=loss, grad_scale=1.0, want_r1=False, want_reg=want_reg,
                             threads=self.m.cfg.threads, bias=self.m.gbias, max_feats=b.max_feats)
+
+    @torch.no_grad()
+    def explain(self, b: Batch) -> tuple[torch.Tensor, torch.Tensor]:
+        t = self.m.table
+        return K.fm_explain(b.offsets, b.ids.to(torch.int32), b.vals, t.v, t.w, self.Kp, bias=self.m.gbias,
+                            threads=self.m.cfg.threads)
 
 
 def dp_dense_blocks(world: int) -> int:

@@ -150,9 +150,8 @@ class ServingModel:
         vals = pg.vals if pg.vals is not None else torch.ones(pg.nnz, dtype=torch.float32, device=d)
         return pg.offsets, pg.ids, vals
 
-    def predict(self, data_lines) -> np.ndarray:
-        from .ops import kernels as Kn
-
+    def _parse(self, data_lines):
+        """(offsets, ids int32, vals, bias or None) of the lines, on the model's device."""
         flat = np.asarray(data_lines).reshape(-1).tolist()
         d = self.device
         parsed = self._parse_gpu(flat) if d.type == "cuda" and flat else None
@@ -163,9 +162,24 @@ class ServingModel:
             offsets, ids, vals = parsed
         gb = self.meta.get("global_bias")
         bias = torch.tensor([gb], dtype=torch.float32, device=d) if gb is not None else None
-        fo = Kn.fm_forward(offsets.to(d), ids.to(torch.int32).to(d), vals.to(d), self.v, self.w, self.Kp,
-                           want_r1=False, bias=bias)
+        return offsets.to(d), ids.to(torch.int32).to(d), vals.to(d), bias
+
+    def predict(self, data_lines) -> np.ndarray:
+        from .ops import kernels as Kn
+
+        offsets, ids, vals, bias = self._parse(data_lines)
+        fo = Kn.fm_forward(offsets, ids, vals, self.v, self.w, self.Kp, want_r1=False, bias=bias)
         return fo.pred.cpu().numpy()
+
+    def explain(self, data_lines) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
+        """``(scores [B], offsets [B + 1], ids [nnz], contrib [nnz])``: the lines parsed as ``predict`` parses
+        them, every occurrence's exact attribution (``ops.kernels.fm_explain``); an example's contributions
+        add up to its score less the global bias."""
+        from .ops import kernels as Kn
+
+        offsets, ids, vals, bias = self._parse(data_lines)
+        contrib, pred = Kn.fm_explain(offsets, ids, vals, self.v, self.w, self.Kp, bias=bias)
+        return pred.cpu().numpy(), offsets.cpu().numpy(), ids.cpu().numpy(), contrib.cpu().numpy()
 
 
 def main(argv=None) -> int:

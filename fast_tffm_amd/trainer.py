@@ -338,6 +338,86 @@ class Trainer:
         return written
 
 
+    # ------------------------------------------------------------------
+    def explain(self, top: int | None = None) -> list[str]:
+        """``run.py explain``: for every predict file, ``<file>_contrib`` (one line per example: the score, then
+        ``id:contribution`` tokens in input order -- with ``top``, the ``top`` largest |contribution| of the
+        line, by descending |c| then position) and ``<file>_importance`` (one line per distinct id:
+        ``id count mean_abs mean``, by descending sum |c| then ascending id).  Ids are table rows (after
+        hashing / modulo).  Multi-rank runs split the examples as ``predict`` does."""
+        from .models.table import bits_for
+        from .ops import kernels as K
+
+        c = self.cfg
+        if top is not None and top < 0:
+            raise ValueError("explain: --top must be >= 0")
+        if not self.restore():
+            raise FileNotFoundError(f"no checkpoint found in {c.log_dir}")
+        self.print("========", "explain", "========")
+        written = []
+        for path in c.predict_files:
+            b = load_file_batch([path], None, c.vocabulary_size, c.hash_feature_id, c.parse_threads)
+            idx = torch.arange(self.rank, b.B, self.world)
+            mine = (_take(b, idx) if self.world > 1 else b).to(self.device)
+            contrib, _ = self.model.explain(mine)
+            pred = self.model.predict(mine)  # (the score ``predict`` writes, bit for bit)
+            ids32 = mine.ids.to(torch.int32)
+            if mine.nnz > 0:
+                dd = K.dedup(ids32, key_bits=bits_for(max(c.vocabulary_size, 2)), want_perm=True)
+                imp = [t.cpu().numpy() for t in K.feature_importance(contrib, dd)]
+            else:
+                imp = [np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0), np.empty(0)]
+            part = (pred.cpu().numpy(), contrib.cpu().numpy(), imp)
+            parts = [part]
+            if self.world > 1:
+                parts = [None] * self.world
+                dist.all_gather_object(parts, part, group=self.ctx.cpu_group)
+            if self.rank != 0:
+                continue
+            offs = b.offsets.numpy().astype(np.int64)
+            ids = b.ids.numpy()
+            scores = np.empty(b.B, dtype=np.float32)
+            full = np.empty(b.nnz, dtype=np.float32)
+            for r, (p_r, c_r, _) in enumerate(parts):
+                scores[r::self.world] = p_r
+                full[_occ_index(offs, np.arange(r, b.B, self.world))] = c_r
+            out = path + "_contrib"
+            with open(out, "w") as f:
+                for i in range(b.B):
+                    s, e = offs[i], offs[i + 1]
+                    pos = np.arange(s, e)
+                    if top is not None:
+                        pos = pos[np.argsort(-np.abs(full[s:e]), kind="stable")[:top]]
+                    toks = [f"{ids[j]}:{str(np.float32(full[j]))}" for j in pos]
+                    f.write(" ".join([str(np.float32(scores[i]))] + toks) + "\n")
+            written.append(out)
+            # importance: the ranks' partial sums merged in rank order, fp64
+            keys = np.concatenate([p[2][0].astype(np.int64) for p in parts])
+            uniq, inv = np.unique(keys, return_inverse=True)
+            count = np.zeros(uniq.size, dtype=np.int64)
+            sum_abs = np.zeros(uniq.size, dtype=np.float64)
+            total = np.zeros(uniq.size, dtype=np.float64)
+            np.add.at(count, inv, np.concatenate([p[2][1].astype(np.int64) for p in parts]))
+            np.add.at(sum_abs, inv, np.concatenate([p[2][2].astype(np.float64) for p in parts]))
+            np.add.at(total, inv, np.concatenate([p[2][3].astype(np.float64) for p in parts]))
+            out = path + "_importance"
+            with open(out, "w") as f:
+                for k in np.lexsort((uniq, -sum_abs)):
+                    f.write(f"{uniq[k]} {count[k]} {str(np.float32(sum_abs[k] / count[k]))} "
+                            f"{str(np.float32(total[k] / count[k]))}\n")
+            written.append(out)
+        self.print("Done. Contributions and importance saved to same directory as predict files")
+        return written
+
+
+def _occ_index(offs: np.ndarray, idx: np.ndarray) -> np.ndarray:
+    """Occurrence positions of examples ``idx`` of a CSR batch, in ``_take``'s order."""
+    sizes = offs[idx + 1] - offs[idx]
+    ends = np.cumsum(sizes)
+    total = int(ends[-1]) if idx.size else 0
+    return np.repeat(offs[idx], sizes) + np.arange(total, dtype=np.int64) - np.repeat(ends - sizes, sizes)
+
+
 def _take(b, idx: torch.Tensor):
     """Sub-batch of examples ``idx`` (host tensors)."""
     from .data.batch import Batch
