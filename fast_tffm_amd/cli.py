@@ -1,4 +1,5 @@
-"""Command line: ``python run.py {train,predict,explain,generate,convert,import_tf,export_tf} CONFIG [options]``.
+"""Command line:
+``python run.py {train,predict,explain,recommend,generate,convert,import_tf,export_tf} CONFIG [options]``.
 
 Same arguments as the reference's run_tffm.py (run_tffm.py:124-162):
   task {train,predict,generate}, config_file,
@@ -7,7 +8,9 @@ Same arguments as the reference's run_tffm.py (run_tffm.py:124-162):
 Extensions: --device {auto,cpu,cuda}, --mode {auto,local,shard,dp,dp_dense},
 --max-steps N, --log-dir DIR (overrides [General] log_dir), the task ``explain CONFIG [--top N]``
 (exact per-feature attributions of the predict files' scores: ``<file>_contrib`` and
-``<file>_importance``, trainer.Trainer.explain; the reference has no equivalent), and the task
+``<file>_importance``, trainer.Trainer.explain; the reference has no equivalent), the task
+``recommend CONFIG --candidates FILE [--top N]`` (for every line of the predict files the N best lines of
+FILE by the score of both taken together: ``<file>_recommend``, trainer.Trainer.recommend), and the task
 ``convert CONFIG --out DIR``: parse the config's train files (+ weight files) once
 into binary CSR caches (``DIR/<name>.fmb``, data/bincache.py) that ``train``
 reads at memory speed when ``train_files`` points at them.  Checkpoint migration:
@@ -33,7 +36,8 @@ import sys
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="run.py", description="MI355X-native distributed factorization machine")
-    p.add_argument("task", choices=["train", "predict", "explain", "generate", "convert", "import_tf", "export_tf"])
+    p.add_argument("task", choices=["train", "predict", "explain", "recommend", "generate", "convert", "import_tf",
+                                    "export_tf"])
     p.add_argument("config_file", type=str)
     p.add_argument("--dist", nargs=4, metavar=("JOB_NAME", "TASK_INDEX", "PS_HOSTS", "WORKER_HOSTS"), default=None,
                    help="For distributed training or prediction")
@@ -51,14 +55,20 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--log-dir", default=None)
     p.add_argument("--out", default=None, help="convert: output directory of the .fmb caches")
     p.add_argument("--top", type=int, default=None, metavar="N",
-                   help="explain: keep only the N largest |contribution| tokens of every line")
+                   help="explain: keep only the N largest |contribution| tokens of every line; "
+                        "recommend: candidates per line (1..128, default 10)")
+    p.add_argument("--candidates", default=None, metavar="FILE",
+                   help="recommend: the candidates, one per line in the predict files' format")
     p.add_argument("--tf_checkpoint", default=None,
                    help="import_tf: TF checkpoint directory (its 'checkpoint' file names the newest) or prefix")
     return p
 
 
 def main(argv: list[str] | None = None) -> int:
-    args = build_parser().parse_args(argv)
+    parser = build_parser()
+    args = parser.parse_args(argv)
+    if args.task == "recommend" and not args.candidates:
+        parser.error("recommend needs --candidates FILE")
     from .config import load_config
     from .parallel import dist as fmdist
 
@@ -82,7 +92,7 @@ def main(argv: list[str] | None = None) -> int:
         # queues (HIP's default 4 makes them share and serialize); before HIP starts
         fmdist.ensure_hw_queues()
 
-    if args.task in ("predict", "explain") and cfg.log_dir is None:
+    if args.task in ("predict", "explain", "recommend") and cfg.log_dir is None:
         print("Missing log directory. Must include a checkpoint file.")
         os._exit(1)
     if args.task == "generate":
@@ -136,6 +146,8 @@ def main(argv: list[str] | None = None) -> int:
             tr.train()
         elif args.task == "explain":
             tr.explain(top=args.top)
+        elif args.task == "recommend":
+            tr.recommend(args.candidates, top=10 if args.top is None else args.top)
         else:
             tr.predict()
     finally:

@@ -9,6 +9,7 @@
 #include <omp.h>
 
 #include "../hash64.h"
+#include "../topk_order.h"
 
 namespace fm {
 namespace cpu {
@@ -327,6 +328,53 @@ void auc(int n, const float* scores, const float* labels, const float* weights, 
   std::sort(kv.begin(), kv.end());
   if (weights) auc_pass<double>(kv, labels, weights, nans, static_cast<double*>(out));
   else auc_pass<uint64_t>(kv, labels, weights, nans, static_cast<uint64_t*>(out));
+}
+
+void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q_stride, const float* C,
+          long long c_stride, const float* qb, const float* cb, int* idx, float* score, int threads) {
+  set_threads(threads);
+  std::vector<int> cols;  // pi(Kp)
+  topk::for_each_col(Kp, [&](int c) { cols.push_back(c); });
+#pragma omp parallel
+  {
+    std::vector<uint64_t> heap;  // min-heap of the best k keys so far
+    std::vector<float> qv(cols.size());
+    heap.reserve(k + 1);
+    const auto gt = [](uint64_t a, uint64_t b) { return a > b; };
+#pragma omp for schedule(dynamic, 1)
+    for (long long q = 0; q < nq; ++q) {
+      const float* qr = Q + q * q_stride;
+      for (size_t i = 0; i < cols.size(); ++i) qv[i] = qr[cols[i]];
+      heap.clear();
+      for (long long c = 0; c < nc; ++c) {
+        const float* cr = C + c * c_stride;
+        float dot = 0.f;
+        for (size_t i = 0; i < cols.size(); ++i) dot = std::fmaf(qv[i], cr[cols[i]], dot);
+        // (two additions as written, then + 0.f: -0 becomes +0)
+        volatile float base = qb[q] + cb[c];
+        volatile float sum = base + dot;
+        const float s = sum + 0.f;
+        uint32_t bits;
+        std::memcpy(&bits, &s, 4);
+        const uint64_t key = topk::make_key(bits, (uint32_t)c);
+        if ((int)heap.size() < k) {
+          heap.push_back(key);
+          std::push_heap(heap.begin(), heap.end(), gt);
+        } else if (key > heap.front()) {
+          std::pop_heap(heap.begin(), heap.end(), gt);
+          heap.back() = key;
+          std::push_heap(heap.begin(), heap.end(), gt);
+        }
+      }
+      std::sort(heap.begin(), heap.end(), gt);
+      for (int t = 0; t < k; ++t) {
+        const uint64_t key = t < (int)heap.size() ? heap[t] : 0ull;
+        const uint32_t sb = topk::key_score_bits(key);
+        idx[q * k + t] = topk::key_index(key);
+        std::memcpy(&score[q * k + t], &sb, 4);
+      }
+    }
+  }
 }
 
 namespace {

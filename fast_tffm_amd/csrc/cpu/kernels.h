@@ -30,6 +30,12 @@ void explain(int B, const int* offsets, const int* rows, const float* vals, cons
              const float* w, long long w_stride, int Kp, int dtype, const float* bias, float* contrib, float* pred,
              int threads);
 
+// The k best candidates of every query from FM profiles (hip/fm_topk.hip: same definition, bit for bit):
+// s = ((qb[q] + cb[c]) + fmaf chain over pi(Kp)) + 0.f, greater s first, equal s by ascending candidate;
+// idx = -1 / score = -inf where nc < k (../topk_order.h).
+void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q_stride, const float* C,
+          long long c_stride, const float* qb, const float* cb, int* idx, float* score, int threads);
+
 // Stable sort of (key, occurrence) + run-length encoding. Returns U.
 int dedup(int n, const uint32_t* keys, uint32_t* skeys, int* perm, uint32_t* uniq, int* seg_start, int* inv,
           const int* ex_of_occ, int* sorted_ex, const float* vals, float* sorted_x);

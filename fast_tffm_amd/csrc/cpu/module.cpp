@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../hash64.h"
+#include "../topk_order.h"
 #include "bincsr.h"
 #include "kernels.h"
 #include "loader.h"
@@ -345,6 +346,24 @@ PYBIND11_MODULE(_fm_cpu, m) {
       py::arg("B"), py::arg("offsets"), py::arg("rows"), py::arg("vals"), py::arg("v"), py::arg("v_stride"),
       py::arg("w"), py::arg("w_stride"), py::arg("Kp"), py::arg("dtype"), py::arg("bias"), py::arg("contrib"),
       py::arg("pred"), py::arg("threads"));
+
+  m.def(
+      "topk_plan",
+      [](long long nq, long long nc, int k) {
+        const fm::topk::Plan p = fm::topk::plan(nq, nc, k);
+        return py::make_tuple(p.slab, p.parts);
+      },
+      py::arg("nq"), py::arg("nc"), py::arg("k"));
+  m.def(
+      "topk",
+      [](long long nq, long long nc, int Kp, int k, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb,
+         u64 cb, u64 idx, u64 score, int threads) {
+        py::gil_scoped_release nogil;
+        fm::cpu::topk(nq, nc, Kp, k, P<const float>(q), q_stride, P<const float>(c), c_stride, P<const float>(qb),
+                      P<const float>(cb), P<int>(idx), P<float>(score), threads);
+      },
+      py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("k"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
+      py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("idx"), py::arg("score"), py::arg("threads"));
 
   m.def(
       "dedup",

@@ -24,6 +24,7 @@ using u64 = std::uintptr_t;
 #include "fm_bwd.hip"
 #include "fm_fwd.hip"
 #include "fm_explain.hip"
+#include "fm_topk.hip"
 #include "dedup.hip"
 #include "auc.hip"
 #include "shard.hip"
@@ -148,6 +149,29 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       },
       py::arg("U"), py::arg("contrib"), py::arg("perm"), py::arg("seg_start"), py::arg("count"), py::arg("sum_abs"),
       py::arg("sum"), py::arg("stream"));
+
+  m.def(
+      "topk_plan",  // (slab, parts) of a top-k call: candidates per slab, partial lists per query (topk_order.h)
+      [](long long nq, long long nc, int k) {
+        const fm::topk::Plan p = fm::topk::plan(nq, nc, k);
+        return py::make_tuple(p.slab, p.parts);
+      },
+      py::arg("nq"), py::arg("nc"), py::arg("k"));
+  m.def("topk_workspace_bytes", &fm::topk_workspace_bytes, py::arg("nq"), py::arg("nc"), py::arg("k"));
+  m.def(
+      "topk",  // the k best candidates of every query from profiles (fm_topk.hip): idx [nq, k], score [nq, k]
+      [](long long nq, long long nc, int Kp, int k, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb,
+         u64 cb, u64 ws, size_t ws_bytes, u64 idx, u64 score, u64 stream) {
+        if ((long long)ws_bytes < fm::topk_workspace_bytes(nq, nc, k)) throw std::runtime_error("topk: workspace too small");
+        fm::TopkArgs a{};
+        a.nq = nq; a.nc = nc; a.Kp = Kp; a.k = k; a.Q = P<const float>(q); a.q_stride = q_stride;
+        a.C = P<const float>(c); a.c_stride = c_stride; a.qb = P<const float>(qb); a.cb = P<const float>(cb);
+        a.ws = P<unsigned long long>(ws); a.idx = P<int>(idx); a.score = P<float>(score);
+        check(fm::launch_topk(a, S(stream)), "fm_topk");
+      },
+      py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("k"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
+      py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("ws"), py::arg("ws_bytes"), py::arg("idx"),
+      py::arg("score"), py::arg("stream"));
 
   m.def(
       "seg_index",

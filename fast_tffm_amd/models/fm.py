@@ -648,15 +648,16 @@ class FactorizationMachine:
 
     # ------------------------------------------------------------------
     @torch.no_grad()
-    def forward(self, b: Batch, *, loss: str = "none", want_reg: bool = False) -> K.FwdOut:
-        """Scores (and optionally the summed loss) without touching parameters."""
+    def forward(self, b: Batch, *, loss: str = "none", want_reg: bool = False, want_r1: bool = False) -> K.FwdOut:
+        """Scores (and optionally the summed loss) without touching parameters; ``want_r1`` also fills
+        ``FwdOut.r1`` (every example's ``sum_j x_j v_j``, a fresh tensor)."""
         if self.closed and self.mode != "local":
             raise RuntimeError("forward on a closed multi-rank FactorizationMachine")
         if self._exchange is not None:
-            return self._exchange.forward(b, loss=loss, want_reg=want_reg)
+            return self._exchange.forward(b, loss=loss, want_reg=want_reg, want_r1=want_r1)
         rows = b.ids.to(torch.int32)
         return K.fm_forward(b.offsets, rows, b.vals, self.table.v, self.table.w, self.Kp, labels=b.labels,
-                            weights=b.weights, loss=loss, grad_scale=1.0, want_r1=False, want_reg=want_reg,
+                            weights=b.weights, loss=loss, grad_scale=1.0, want_r1=want_r1, want_reg=want_reg,
                             threads=self.cfg.threads, bias=self.gbias, max_feats=b.max_feats)
 
     def predict(self, b: Batch) -> torch.Tensor:
@@ -674,6 +675,30 @@ class FactorizationMachine:
             return self._exchange.explain(b)
         return K.fm_explain(b.offsets, b.ids.to(torch.int32), b.vals, self.table.v, self.table.w, self.Kp,
                             bias=self.gbias, threads=self.cfg.threads)
+
+    @torch.no_grad()
+    def profile(self, b: Batch) -> tuple[torch.Tensor, torch.Tensor]:
+        """``(pred [B], S [B, Kp])`` of the examples of ``b``: the score and ``S = sum_j x_j v_j``, the two
+        ingredients of ranking by parts.  For feature sets A and B, ``score(A + B) = score(A) + score(B) -
+        bias + <S_A, S_B>`` exactly (repeated ids are separate occurrences), so one forward per context and
+        per candidate replaces one per pair.  A collective on a row-sharded model, as ``forward`` is."""
+        if self.cfg.dtype not in (torch.float32, torch.bfloat16):
+            raise NotImplementedError(
+                "profile / recommend need fp32 S: the forward keeps r1 in bf16 for fp8 tables, so the "
+                "score identity would not hold to fp32 accuracy")
+        fo = self.forward(b, want_r1=True)
+        return fo.pred, fo.r1
+
+    @torch.no_grad()
+    def recommend(self, contexts: Batch, candidates, k: int) -> tuple[torch.Tensor, torch.Tensor]:
+        """The ``k`` best candidates of every context: ``(idx [B, k] int32, score [B, k] fp32)``, the score of
+        the context's and the candidate's features taken together (``K.fm_topk``: greater first, ties by
+        ascending candidate, -1 / -inf past the candidate count).  ``candidates``: a ``Batch`` of candidate
+        examples, or the ``(pred, S)`` pair ``profile`` returned for one (profile a catalogue once)."""
+        c_pred, c_prof = self.profile(candidates) if isinstance(candidates, Batch) else candidates
+        q_pred, q_prof = self.profile(contexts)
+        c_base = c_pred - self.gbias if self.gbias is not None else c_pred
+        return K.fm_topk(q_prof, q_pred, c_prof, c_base, k, threads=self.cfg.threads)
 
     def eval_loss(self, b: Batch) -> float:
         """Weighted mean loss of the configured type (reference valid_op, fm_model.py:317-333)."""

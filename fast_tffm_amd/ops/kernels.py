@@ -940,6 +940,83 @@ def auc(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None
 
 
 # ---------------------------------------------------------------------------
+# top-k recommendation: rank a candidate set per query from FM profiles
+# ---------------------------------------------------------------------------
+TOPK_MAX_K = 128
+TOPK_MAX_KP = 256
+
+
+def topk_plan(nq: int, nc: int, k: int) -> tuple[int, int]:
+    """``(slab, parts)`` of an ``fm_topk`` call on the GPU: the candidates per slab and the partial lists per
+    query (csrc/topk_order.h; a pure function of the sizes, the same from the host module)."""
+    return tuple(native.cpu().topk_plan(int(nq), int(nc), int(k)))
+
+
+def topk_workspace(nq: int, nc: int, k: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of ``fm_topk`` (GPU): the slabs' partial key lists."""
+    return torch.empty(int(native.hip().topk_workspace_bytes(int(nq), int(nc), int(k))), dtype=torch.uint8,
+                       device=device)
+
+
+def _chk_profiles(t: torch.Tensor, base: torch.Tensor, name: str, dev: torch.device) -> tuple[int, int, int]:
+    """Validate a profile matrix [n, Kp] (+ its base scores [n]); returns (n, Kp, row stride)."""
+    _check(t.dim() == 2, f"{name}_prof: expected [n, Kp]")
+    _check(t.dtype == torch.float32, f"{name}_prof: expected {torch.float32}, got {t.dtype}")
+    _check(t.device == dev, f"{name}_prof: expected device {dev}, got {t.device}")
+    n, Kp = t.shape
+    _check(Kp % 4 == 0 and 4 <= Kp <= TOPK_MAX_KP, f"{name}_prof: Kp={Kp} must be a multiple of 4 in 4..{TOPK_MAX_KP}")
+    _check(t.stride(1) == 1, f"{name}_prof: rows must be contiguous")
+    stride = t.stride(0) if n > 1 else Kp  # (the stride of a single row is never used)
+    _check(stride >= Kp and stride % 4 == 0, f"{name}_prof: row stride {stride} must be a multiple of 4 >= Kp")
+    _check(n == 0 or t.data_ptr() % 16 == 0, f"{name}_prof: base must be 16-byte aligned")
+    _chk_vec(base, torch.float32, n, f"{name}_base", dev)
+    _check(base.numel() == n, f"{name}_base: one base score per profile row")
+    return n, Kp, stride
+
+
+def fm_topk(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_base: torch.Tensor, k: int, *,
+            idx: torch.Tensor | None = None, score: torch.Tensor | None = None, ws: torch.Tensor | None = None,
+            threads: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+    """The ``k`` best candidates of every query from FM profiles (hip/fm_topk.hip; the reference only scores).
+
+    ``s(q, c) = ((q_base[q] + c_base[c]) + dot) + 0`` with ``dot`` the fp32 fmaf chain of ``q_prof[q]`` and
+    ``c_prof[c]`` over the columns in the fixed order of csrc/topk_order.h.  Returns ``(idx [nq, k] int32,
+    score [nq, k] fp32)``: greater score first, equal scores by ascending candidate, ``-1`` / ``-inf`` where
+    there are fewer than ``k`` candidates.  Exact fp32 on the matrix cores (gfx950's fp32-input MFMA), bitwise
+    reproducible, and bit for bit the same on the CPU.  GPU: current stream, no host synchronisation (``ws``:
+    reusable ``topk_workspace``).  Profiles are expected to be finite."""
+    dev = q_prof.device
+    _check(isinstance(k, int) and 1 <= k <= TOPK_MAX_K, f"fm_topk: k must be in 1..{TOPK_MAX_K}, got {k}")
+    nq, Kp, q_stride = _chk_profiles(q_prof, q_base, "q", dev)
+    nc, Kc, c_stride = _chk_profiles(c_prof, c_base, "c", dev)
+    _check(Kp == Kc, f"fm_topk: profile widths differ ({Kp} and {Kc})")
+    _check(nc < 2**31 and nq < 2**31, "fm_topk: nq and nc must be below 2^31")
+    if idx is None:
+        idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
+    if score is None:
+        score = torch.empty((nq, k), dtype=torch.float32, device=dev)
+    _chk_vec(idx, torch.int32, nq * k, "idx", dev)
+    _chk_vec(score, torch.float32, nq * k, "score", dev)
+    _check(tuple(idx.shape) == (nq, k) and tuple(score.shape) == (nq, k), "idx / score: expected [nq, k]")
+    if nq == 0:
+        return idx, score
+    kw = dict(nq=nq, nc=nc, Kp=Kp, k=k, q=_p(q_prof), q_stride=q_stride, c=_p(c_prof), c_stride=c_stride,
+              qb=_p(q_base), cb=_p(c_base), idx=_p(idx), score=_p(score))
+    if _is_gpu(q_prof):
+        h = native.hip()
+        need = int(h.topk_workspace_bytes(nq, nc, k))
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _chk_vec(ws, torch.uint8, need, "ws", dev)
+        _check(ws.data_ptr() % 8 == 0, "ws: must be 8-byte aligned")
+        h.topk(ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(q_prof), **kw)
+    else:
+        _check(ws is None, "fm_topk: the workspace is a GPU argument")
+        native.cpu().topk(threads=threads, **kw)
+    return idx, score
+
+
+# ---------------------------------------------------------------------------
 # sparse checkpoints: rows that differ from their initial state
 # ---------------------------------------------------------------------------
 def _bits_of(value: float, dtype: torch.dtype) -> int:

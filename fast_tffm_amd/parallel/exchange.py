@@ -1189,7 +1189,7 @@ class ShardExchange(_Base):
         return StepOut(loss, b.B)
 
     @torch.no_grad()
-    def forward(self, b: Batch, *, loss: str = "none", want_reg: bool = False) -> K.FwdOut:
+    def forward(self, b: Batch, *, loss: str = "none", want_reg: bool = False, want_r1: bool = False) -> K.FwdOut:
         self.flush()  # (staleness: evaluate the table with every update applied)
         self.m.ws.ensure(b.B, b.nnz)
         pl = self._take_plan(b, False)
@@ -1198,7 +1198,7 @@ class ShardExchange(_Base):
         src_v, src_w = self.wire.views(buf)
         seg = getattr(part, "seg", None)  # (eval plans keep the inverse map: train=False)
         out = K.fm_forward(b.offsets, part.keys if seg is not None else part.dd.inv[: b.nnz], b.vals, src_v, src_w,
-                           self.Kp, labels=b.labels, weights=b.weights, loss=loss, grad_scale=1.0, want_r1=False,
+                           self.Kp, labels=b.labels, weights=b.weights, loss=loss, grad_scale=1.0, want_r1=want_r1,
                            want_reg=want_reg, threads=self.m.cfg.threads, bias=self.m.gbias, seg_lookup=seg)
         if self.dev.type == "cuda":
             done = torch.cuda.Event()
@@ -1278,10 +1278,10 @@ class DPExchange(_Base):
         return StepOut(fo.loss_sum, b.B)
 
     @torch.no_grad()
-    def forward(self, b: Batch, *, loss: str = "none", want_reg: bool = False) -> K.FwdOut:
+    def forward(self, b: Batch, *, loss: str = "none", want_reg: bool = False, want_r1: bool = False) -> K.FwdOut:
         t = self.m.table
         return K.fm_forward(b.offsets, b.ids.to(torch.int32), b.vals, t.v, t.w, self.Kp, labels=b.labels,
-                            weights=b.weights, loss=loss, grad_scale=1.0, want_r1=False, want_reg=want_reg,
+                            weights=b.weights, loss=loss, grad_scale=1.0, want_r1=want_r1, want_reg=want_reg,
                             threads=self.m.cfg.threads, bias=self.m.gbias, max_feats=b.max_feats)
 
     @torch.no_grad()

@@ -181,6 +181,44 @@ class ServingModel:
         contrib, pred = Kn.fm_explain(offsets, ids, vals, self.v, self.w, self.Kp, bias=bias)
         return pred.cpu().numpy(), offsets.cpu().numpy(), ids.cpu().numpy(), contrib.cpu().numpy()
 
+    def _profile(self, data_lines) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor | None]:
+        """(score [B], S [B, Kp], bias or None) of the lines, on the model's device."""
+        from .ops import kernels as Kn
+
+        offsets, ids, vals, bias = self._parse(data_lines)
+        fo = Kn.fm_forward(offsets, ids, vals, self.v, self.w, self.Kp, want_r1=True, bias=bias)
+        return fo.pred, fo.r1, bias
+
+    def index(self, candidate_lines) -> "CandidateIndex":
+        """Profile a catalogue once: the object ``recommend`` takes in place of candidate lines (it keeps
+        every candidate's score less the global bias and its ``S = sum_j x_j v_j`` on the device)."""
+        pred, prof, bias = self._profile(candidate_lines)
+        return CandidateIndex(prof, pred - bias if bias is not None else pred)
+
+    def recommend(self, data_lines, candidates, top: int = 10) -> tuple[np.ndarray, np.ndarray]:
+        """``(idx [B, top] int32, score [B, top] fp32)``: for every context line the ``top`` candidates of
+        greatest score of the context's and the candidate's features taken together, best first, equal scores
+        by ascending candidate number; -1 / -inf past the number of candidates (``ops.kernels.fm_topk``).
+        ``candidates``: lines in the same format, or the ``index`` of them."""
+        from .ops import kernels as Kn
+
+        ci = candidates if isinstance(candidates, CandidateIndex) else self.index(candidates)
+        pred, prof, _ = self._profile(data_lines)
+        idx, score = Kn.fm_topk(prof, pred, ci.prof, ci.base, int(top))
+        return idx.cpu().numpy(), score.cpu().numpy()
+
+
+class CandidateIndex:
+    """Profiles of a candidate catalogue on the serving device (``ServingModel.index``)."""
+
+    __slots__ = ("prof", "base")
+
+    def __init__(self, prof: torch.Tensor, base: torch.Tensor):
+        self.prof, self.base = prof, base
+
+    def __len__(self) -> int:
+        return self.prof.shape[0]
+
 
 def main(argv=None) -> int:
     ap = argparse.ArgumentParser(description="Run a fast_tffm_amd serving export (saved_model_cli run equivalent)")

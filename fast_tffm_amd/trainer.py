@@ -410,6 +410,64 @@ class Trainer:
         return written
 
 
+    # ------------------------------------------------------------------
+    def recommend(self, candidates: str, top: int = 10) -> list[str]:
+        """``run.py recommend``: rank the candidates of file ``candidates`` (one per line, the predict files'
+        format; the label column is read and ignored) for every line of the predict files.  Writes
+        ``<file>_recommend``: line i holds up to ``top`` tokens ``c:score``, best first (equal scores by
+        ascending c), c the 0-based line number of the candidate and the score that of the context's and the
+        candidate's features taken together (``FactorizationMachine.recommend``).  Multi-rank runs deal the
+        contexts as ``predict`` does; every rank profiles all candidates."""
+        from .ops import kernels as K
+
+        c = self.cfg
+        if not isinstance(top, int) or not 1 <= top <= K.TOPK_MAX_K:
+            raise ValueError(f"recommend: --top must be in 1..{K.TOPK_MAX_K}, got {top}")
+        if not self.restore():
+            raise FileNotFoundError(f"no checkpoint found in {c.log_dir}")
+        self.print("========", "recommend", "========")
+        cands = load_file_batch([candidates], None, c.vocabulary_size, c.hash_feature_id, c.parse_threads)
+        preds, profs = [], []
+        for s0 in range(0, cands.B, RECOMMEND_PROFILE_BATCH):  # (a collective per chunk on a row-sharded model)
+            part = _take(cands, torch.arange(s0, min(s0 + RECOMMEND_PROFILE_BATCH, cands.B))).to(self.device)
+            p, s = self.model.profile(part)
+            preds.append(p)
+            profs.append(s)
+        if preds:
+            index = (torch.cat(preds), torch.cat(profs))
+        else:
+            index = (torch.empty(0, dtype=torch.float32, device=self.device),
+                     torch.empty((0, self.model.Kp), dtype=torch.float32, device=self.device))
+        written = []
+        for path in c.predict_files:
+            b = load_file_batch([path], None, c.vocabulary_size, c.hash_feature_id, c.parse_threads)
+            mine = (_take(b, torch.arange(self.rank, b.B, self.world)) if self.world > 1 else b).to(self.device)
+            idx, score = self.model.recommend(mine, index, top)
+            part = (idx.cpu().numpy(), score.cpu().numpy())
+            parts = [part]
+            if self.world > 1:
+                parts = [None] * self.world
+                dist.all_gather_object(parts, part, group=self.ctx.cpu_group)
+            if self.rank != 0:
+                continue
+            full_i = np.empty((b.B, top), dtype=np.int32)
+            full_s = np.empty((b.B, top), dtype=np.float32)
+            for r, (i_r, s_r) in enumerate(parts):
+                full_i[r::self.world] = i_r
+                full_s[r::self.world] = s_r
+            out = path + "_recommend"
+            with open(out, "w") as f:
+                for i in range(b.B):
+                    f.write(" ".join(f"{ci}:{str(np.float32(sc))}" for ci, sc in zip(full_i[i], full_s[i]) if ci >= 0)
+                            + "\n")
+            written.append(out)
+        self.print("Done. Recommendations saved to same directory as predict files")
+        return written
+
+
+RECOMMEND_PROFILE_BATCH = 65536  # candidate lines per forward pass of ``Trainer.recommend``
+
+
 def _occ_index(offs: np.ndarray, idx: np.ndarray) -> np.ndarray:
     """Occurrence positions of examples ``idx`` of a CSR batch, in ``_take``'s order."""
     sizes = offs[idx + 1] - offs[idx]
