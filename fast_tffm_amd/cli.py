@@ -1,5 +1,5 @@
 """Command line:
-``python run.py {train,predict,explain,recommend,generate,convert,import_tf,export_tf} CONFIG [options]``.
+``python run.py {train,predict,evaluate,explain,recommend,generate,convert,import_tf,export_tf} CONFIG [options]``.
 
 Same arguments as the reference's run_tffm.py (run_tffm.py:124-162):
   task {train,predict,generate}, config_file,
@@ -10,7 +10,9 @@ Extensions: --device {auto,cpu,cuda}, --mode {auto,local,shard,dp,dp_dense},
 (exact per-feature attributions of the predict files' scores: ``<file>_contrib`` and
 ``<file>_importance``, trainer.Trainer.explain; the reference has no equivalent), the task
 ``recommend CONFIG --candidates FILE [--top N]`` (for every line of the predict files the N best lines of
-FILE by the score of both taken together: ``<file>_recommend``, trainer.Trainer.recommend), and the task
+FILE by the score of both taken together: ``<file>_recommend``, trainer.Trainer.recommend), the task
+``evaluate CONFIG`` (loss and ROC AUC of the checkpoint on the labelled predict files and, with ``[Predict]
+predict_group_files``, the grouped AUC and ``<file>_gauc``: trainer.Trainer.evaluate), and the task
 ``convert CONFIG --out DIR``: parse the config's train files (+ weight files) once
 into binary CSR caches (``DIR/<name>.fmb``, data/bincache.py) that ``train``
 reads at memory speed when ``train_files`` points at them.  Checkpoint migration:
@@ -36,8 +38,8 @@ import sys
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="run.py", description="MI355X-native distributed factorization machine")
-    p.add_argument("task", choices=["train", "predict", "explain", "recommend", "generate", "convert", "import_tf",
-                                    "export_tf"])
+    p.add_argument("task", choices=["train", "predict", "evaluate", "explain", "recommend", "generate", "convert",
+                                    "import_tf", "export_tf"])
     p.add_argument("config_file", type=str)
     p.add_argument("--dist", nargs=4, metavar=("JOB_NAME", "TASK_INDEX", "PS_HOSTS", "WORKER_HOSTS"), default=None,
                    help="For distributed training or prediction")
@@ -92,7 +94,7 @@ def main(argv: list[str] | None = None) -> int:
         # queues (HIP's default 4 makes them share and serialize); before HIP starts
         fmdist.ensure_hw_queues()
 
-    if args.task in ("predict", "explain", "recommend") and cfg.log_dir is None:
+    if args.task in ("predict", "evaluate", "explain", "recommend") and cfg.log_dir is None:
         print("Missing log directory. Must include a checkpoint file.")
         os._exit(1)
     if args.task == "generate":
@@ -144,6 +146,8 @@ def main(argv: list[str] | None = None) -> int:
     try:
         if args.task == "train":
             tr.train()
+        elif args.task == "evaluate":
+            tr.evaluate()
         elif args.task == "explain":
             tr.explain(top=args.top)
         elif args.task == "recommend":

@@ -27,8 +27,14 @@ Extensions (new keys, all optional):
                 validation_auc = true|false (exact weighted ROC AUC of the validation scores, printed and logged
                                 after the validation loss; default false), auc_tolerance = <float> (stop when
                                 the validation AUC is >= it; needs validation_auc and validation_files),
+                validation_group_files = <files> (one group key per line, parallel to validation_files),
+                validation_gauc = true|false (grouped AUC of the validation scores, printed and logged after the
+                                AUC / loss lines; needs validation_group_files; default false),
+                gauc_tolerance = <float> (stop when the validation GAUC is >= it; needs validation_gauc),
                 checkpoint_format = dense|sparse (sparse: a checkpoint stores only the rows that differ from
                                 their counter-based init, and restore regenerates the others; default dense)
+  [Predict]     predict_group_files = <files> (one group key per line, parallel to predict_files: the
+                                ``evaluate`` task then reports the grouped AUC and writes <file>_gauc)
   [Distributed] mode = auto|local|shard|dp|dp_dense, grad_reduce = sum|mean,
                 comm_dtype = auto|fp32|bf16 (row-sharded wire rows; auto = table storage dtype),
                 microbatches = 1|2|... (row-sharded step parts overlapping the exchange; default 1),
@@ -115,8 +121,12 @@ class FMRunConfig:
     validation_auc: bool = False        # report the exact weighted ROC AUC next to the validation loss
     auc_tolerance: float | None = None  # stop when the validation AUC is >= this
     checkpoint_format: str = "dense"    # dense (every row) | sparse (rows that differ from their init)
+    validation_group_files: list[str] = field(default_factory=list)  # one group key per validation line
+    validation_gauc: bool = False        # report the grouped AUC of the validation scores
+    gauc_tolerance: float | None = None  # stop when the validation GAUC is >= this
     # [Predict]
     predict_files: list[str] = field(default_factory=list)
+    predict_group_files: list[str] = field(default_factory=list)  # one group key per predict line (evaluate)
     # [Distributed]
     mode: str = "auto"
     grad_reduce: str = "sum"
@@ -258,10 +268,28 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
             raise ConfigError("The numbers of validation data files and validation weight files do not match.")
     if c.auc_tolerance is not None and not (c.validation_auc and c.validation_data_files):
         raise ConfigError("auc_tolerance needs validation_auc = true and validation_files.")
+    vgf = read_list(TRAIN, "validation_group_files", required=False)
+    if vgf is not None:
+        if not c.validation_data_files:
+            raise ConfigError("validation_group_files needs validation_files.")
+        c.validation_group_files = _expand(vgf, base_dir)
+        if len(c.validation_data_files) != len(c.validation_group_files):
+            raise ConfigError("The numbers of validation data files and validation group files do not match.")
+    c.validation_gauc = opt(TRAIN, "validation_gauc", to_bool, c.validation_gauc)
+    c.gauc_tolerance = opt(TRAIN, "gauc_tolerance", float, c.gauc_tolerance)
+    if c.validation_gauc and not c.validation_group_files:
+        raise ConfigError("validation_gauc needs validation_group_files.")
+    if c.gauc_tolerance is not None and not c.validation_gauc:
+        raise ConfigError("gauc_tolerance needs validation_gauc = true and validation_group_files.")
 
     pf = read_list(PREDICT, "predict_files", required=False)
     if pf is not None:
         c.predict_files = _expand(pf, base_dir)
+    pgf = read_list(PREDICT, "predict_group_files", required=False)
+    if pgf is not None:
+        c.predict_group_files = _expand(pgf, base_dir)
+        if len(c.predict_files) != len(c.predict_group_files):
+            raise ConfigError("The numbers of predict files and predict group files do not match.")
 
     c.mode = opt(DISTRIBUTED, "mode", lambda s: s.strip().lower(), c.mode)
     c.grad_reduce = opt(DISTRIBUTED, "grad_reduce", lambda s: s.strip().lower(), c.grad_reduce)

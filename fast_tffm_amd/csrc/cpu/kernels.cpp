@@ -330,6 +330,77 @@ void auc(int n, const float* scores, const float* labels, const float* weights, 
   else auc_pass<uint64_t>(kv, labels, weights, nans, static_cast<uint64_t*>(out));
 }
 
+namespace {
+// One pass per group over the (group, key, index) order; a group's runs of equal keys as in auc_pass.
+template <typename T>
+void gauc_pass(const std::vector<std::pair<uint64_t, uint32_t>>& kv, long long G, const float* labels,
+               const float* weights, uint64_t nans, void* out, T* rec) {
+  const size_t n = kv.size();
+  std::fill(rec, rec + 3 * static_cast<size_t>(G), static_cast<T>(0));
+  double wa = 0.0;
+  T wsum = 0;
+  uint64_t valid = 0, exs = 0;
+  for (size_t j = 0; j < n;) {
+    const uint32_t g = static_cast<uint32_t>(kv[j].first >> 32);
+    const size_t first = j;
+    T u2 = 0, p = 0, nlt = 0;
+    while (j < n && static_cast<uint32_t>(kv[j].first >> 32) == g) {
+      const uint64_t gk = kv[j].first;
+      T rp = 0, rn = 0;
+      for (; j < n && kv[j].first == gk; ++j) {
+        const uint32_t i = kv[j].second;
+        const T w = weights ? static_cast<T>(weights[i]) : static_cast<T>(1);
+        if (labels[i] > 0.f) rp += w;
+        else rn += w;
+      }
+      const T nle = nlt + rn;
+      u2 += rp * (nlt + nle);
+      p += rp;
+      nlt = nle;
+    }
+    T* r = rec + 3 * static_cast<size_t>(g);
+    r[0] = u2;
+    r[1] = p;
+    r[2] = nlt;
+    if (p > 0 && nlt > 0) {
+      const T w = p + nlt;
+      wa += static_cast<double>(w) *
+            (static_cast<double>(u2) / (2.0 * static_cast<double>(p) * static_cast<double>(nlt)));
+      wsum += w;
+      ++valid;
+      exs += j - first;
+    }
+  }
+  unsigned char* o = static_cast<unsigned char*>(out);
+  const uint64_t zero = 0;
+  std::memcpy(o, &wa, 8);
+  std::memcpy(o + 8, &wsum, 8);
+  std::memcpy(o + 16, &valid, 8);
+  std::memcpy(o + 24, &exs, 8);
+  std::memcpy(o + 32, &nans, 8);
+  std::memcpy(o + 40, &zero, 8);
+}
+}  // namespace
+
+void gauc(int n, long long G, const float* scores, const float* labels, const float* weights, const int* groups,
+          void* out, void* rec) {
+  std::vector<std::pair<uint64_t, uint32_t>> kv(n > 0 ? n : 0);
+  uint64_t nans = 0;
+  for (int j = 0; j < n; ++j) {
+    uint32_t b;
+    std::memcpy(&b, scores + j, 4);
+    nans += (b & 0x7fffffffu) > 0x7f800000u;
+    if (b == 0x80000000u) b = 0u;
+    const uint32_t key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    const uint32_t g = static_cast<uint32_t>(groups[j]) < static_cast<uint64_t>(G) ? static_cast<uint32_t>(groups[j])
+                                                                                  : static_cast<uint32_t>(G - 1);
+    kv[j] = {(static_cast<uint64_t>(g) << 32) | key, static_cast<uint32_t>(j)};
+  }
+  std::sort(kv.begin(), kv.end());
+  if (weights) gauc_pass<double>(kv, G, labels, weights, nans, out, static_cast<double*>(rec));
+  else gauc_pass<uint64_t>(kv, G, labels, weights, nans, out, static_cast<uint64_t*>(rec));
+}
+
 void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q_stride, const float* C,
           long long c_stride, const float* qb, const float* cb, int* idx, float* score, int threads) {
   set_threads(threads);

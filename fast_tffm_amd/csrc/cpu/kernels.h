@@ -58,6 +58,13 @@ void csr_rows(int B, const int* offsets, int* ex_of_occ);
 // scores, 0 -- uint64 when weights is null (exact), else fp64 summed in sorted order.
 void auc(int n, const float* scores, const float* labels, const float* weights, void* out);
 
+// Grouped AUC statistics (hip/gauc.hip: same definition, same two modes) of n scores with group ids in [0, G)
+// (ids outside it count as G - 1): rec[G, 3] = U2_g, P_g, N_g of every group (uint64 when weights is null, else
+// fp64 summed in (group, score) order) and out[6], 64-bit words = sum over the valid groups of W_g AUC_g (fp64),
+// their sum of W_g (uint64 / fp64), their number, their examples, the NaN scores, 0.
+void gauc(int n, long long G, const float* scores, const float* labels, const float* weights, const int* groups,
+          void* out, void* rec);
+
 // Counter-based U(-range, range) init, identical to the gfx950 init_rows kernel.
 void init_rows(void* v, long long v_stride, float* w, long long w_stride, long long rows, int K, int Kp, int dtype,
                long long gid_mul, long long gid_add, unsigned long long seed, float range, int threads);

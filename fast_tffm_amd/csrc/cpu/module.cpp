@@ -472,4 +472,14 @@ PYBIND11_MODULE(_fm_cpu, m) {
         fm::cpu::auc(n, P<const float>(scores), P<const float>(labels), P<const float>(weights), P<void>(out));
       },
       py::arg("n"), py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("out"));
+
+  m.def(
+      "gauc",
+      [](int n, long long G, u64 scores, u64 labels, u64 weights, u64 groups, u64 out, u64 rec) {
+        py::gil_scoped_release nogil;
+        fm::cpu::gauc(n, G, P<const float>(scores), P<const float>(labels), P<const float>(weights),
+                      P<const int>(groups), P<void>(out), P<void>(rec));
+      },
+      py::arg("n"), py::arg("G"), py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("groups"),
+      py::arg("out"), py::arg("rec"));
 }

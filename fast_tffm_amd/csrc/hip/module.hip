@@ -27,6 +27,7 @@ using u64 = std::uintptr_t;
 #include "fm_topk.hip"
 #include "dedup.hip"
 #include "auc.hip"
+#include "gauc.hip"
 #include "shard.hip"
 #include "init.hip"
 #include "ckpt.hip"
@@ -314,6 +315,29 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       },
       py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("n"), py::arg("out"), py::arg("ws"),
       py::arg("ws_bytes"), py::arg("stream"));
+
+  m.def(
+      "gauc_workspace_bytes",
+      [](long long n, long long G) {
+        const size_t b = fm::gauc_workspace_bytes(n, G);
+        if (!b) throw std::invalid_argument("gauc: n must be in [0, 2^30) and num_groups in [1, 2^31)");
+        return b;
+      },
+      py::arg("n"), py::arg("G"));
+  m.def(
+      "gauc",  // grouped AUC: per-group [U2, P, N] into rec[G, 3] and the record [sum W AUC (fp64), sum W, valid
+               // groups, examples in valid groups, nan count, sort error word] into out[6] (64-bit words; the
+               // weight sums int64 when weights == 0, else fp64); asynchronous (ops/kernels.py GaucStats)
+      [](u64 scores, u64 labels, u64 weights, u64 groups, int n, long long G, u64 out, u64 rec, u64 ws,
+         size_t ws_bytes, u64 stream) {
+        const int rc = fm::launch_gauc(P<const float>(scores), P<const float>(labels), P<const float>(weights),
+                                       P<const int>(groups), n, G, P<void>(out), P<void>(rec), P<void>(ws), ws_bytes,
+                                       S(stream));
+        if (rc == -6) throw std::invalid_argument("gauc: num_groups must be in [1, 2^31)");
+        check(rc, "gauc");
+      },
+      py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("groups"), py::arg("n"), py::arg("G"),
+      py::arg("out"), py::arg("rec"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
 
   m.def(
       "gather_rows",

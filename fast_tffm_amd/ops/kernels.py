@@ -940,6 +940,120 @@ def auc(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None
 
 
 # ---------------------------------------------------------------------------
+# validation metric: grouped AUC (GAUC)
+# ---------------------------------------------------------------------------
+class GaucStats:
+    """The record of one ``gauc`` call, on the op's device: six 64-bit words ``[sum over the valid groups of
+    W_g AUC_g (fp64), their sum of W_g, valid groups, examples in valid groups, NaN scores, sort error word]``
+    (the sum of W_g is an integer without weights, fp64 with them) and ``groups``, the ``[G, 3]`` per-group
+    ``(U2_g, P_g, N_g)`` (int64 / float64).  The readers synchronise with the launch chain on the GPU and raise
+    when its sort reported a failed look-back: never a number then."""
+
+    __slots__ = ("rec", "groups", "weighted", "n", "num_groups", "done")
+
+    def __init__(self, rec: torch.Tensor, groups: torch.Tensor, weighted: bool, n: int, num_groups: int,
+                 done: "torch.cuda.Event | None" = None):
+        self.rec, self.groups, self.weighted, self.n, self.num_groups = rec, groups, weighted, n, num_groups
+        self.done = done  # GPU: recorded behind the launch chain, on its stream
+
+    def stats(self) -> tuple:
+        """(sum W AUC, sum W, valid groups, examples in valid groups, nans) on the host."""
+        if self.done is not None:  # (the reader's current stream need not be the chain's)
+            self.done.synchronize()
+        r = self.rec.cpu()
+        f = r.view(torch.float64).tolist()
+        i = r.tolist()
+        if i[5]:
+            raise RuntimeError(f"gauc: the radix sort's look-back spin bound was hit (error word {i[5]}); "
+                               "no GAUC for this input")
+        return f[0], (f[1] if self.weighted else i[1]), i[2], i[3], i[4]
+
+    def value(self) -> float:
+        """sum W_g AUC_g / sum W_g over the valid groups; NaN when there is none or a score is NaN."""
+        wa, w, valid, _, nans = self.stats()
+        if nans or not valid or not w > 0:
+            return float("nan")
+        return wa / w
+
+    def valid_groups(self) -> int:
+        """Groups with positive and negative weight (the ones GAUC averages)."""
+        return self.stats()[2]
+
+    def coverage(self) -> float:
+        """Share of the examples that lie in valid groups (NaN for an empty set)."""
+        return self.stats()[3] / self.n if self.n else float("nan")
+
+    def per_group(self) -> torch.Tensor:
+        """The ``[G, 3]`` tensor ``(U2_g, P_g, N_g)`` on the op's device; zeros for empty groups."""
+        self.stats()
+        return self.groups
+
+
+def gauc_workspace(n: int, num_groups: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of ``gauc`` for up to ``n`` scores in ``num_groups`` groups (GPU)."""
+    return torch.empty(int(native.hip().gauc_workspace_bytes(int(n), int(num_groups))), dtype=torch.uint8,
+                       device=device)
+
+
+def gauc(scores: torch.Tensor, labels: torch.Tensor, groups: torch.Tensor, num_groups: int,
+         weights: torch.Tensor | None = None, *, ws: torch.Tensor | None = None) -> GaucStats:
+    """Grouped AUC statistics of raw scores: ``auc``'s statistics of every group on its own, and their mean.
+
+    ``groups``: int32 ids in ``[0, num_groups)``, one per score (a user, a query, a session).  Per group g, with
+    ``auc``'s conventions (positive iff ``label > 0``, the same score order, a tie counts one half): P_g, N_g,
+    U2_g over the group's examples only; g is valid iff P_g > 0 and N_g > 0, AUC_g = U2_g / (2 P_g N_g), W_g =
+    P_g + N_g and GAUC = sum_valid W_g AUC_g / sum_valid W_g -- NaN without a valid group or with a NaN score.
+    Unweighted per-group records are integers (exact, the same on GPU and CPU); weighted ones are fp64 sums of
+    the group's own non-negative terms in a fixed order (bitwise the same run to run).  GPU: hip/gauc.hip on
+    the current stream (``ws``: reusable ``gauc_workspace``); CPU: a sort and one pass per group.  ``n == 0``
+    launches nothing (NaN).  Ids outside the range are an error with FM_DEBUG_CHECKS=1 and count as the last
+    group without it.
+    """
+    dev = scores.device
+    n = scores.numel()
+    G = int(num_groups)
+    _chk_vec(scores, torch.float32, n, "scores", dev)
+    _chk_vec(labels, torch.float32, n, "labels", dev)
+    _chk_vec(groups, torch.int32, n, "groups", dev)
+    _chk_vec(weights, torch.float32, n, "weights", dev)
+    _check(labels.numel() == n and groups.numel() == n and (weights is None or weights.numel() == n),
+           "gauc: one label / group / weight per score")
+    _check(n < 2**30, "gauc: n must be < 2^30 (the radix sort's bound)")
+    _check(1 <= G < 2**31, "gauc: num_groups must be in [1, 2^31)")
+    weighted = weights is not None
+    if _DEBUG and n > 0 and not (scores.is_cuda and torch.cuda.is_current_stream_capturing()):
+        _check(bool(groups.min() >= 0) and bool(groups.max() < G), "groups: ids must be in [0, num_groups)")
+        if weighted:
+            _check(bool(weights.min() >= 0), "weights: must be >= 0")
+    rdt = torch.float64 if weighted else torch.int64
+    if n == 0:  # (host records: nothing is launched)
+        return GaucStats(torch.zeros(6, dtype=torch.int64), torch.zeros((G, 3), dtype=rdt), weighted, 0, G)
+    rec = torch.empty(6, dtype=torch.int64, device=dev)
+    per = torch.empty((G, 3), dtype=rdt, device=dev)
+    if _is_gpu(scores):
+        h = native.hip()
+        _sort_selfcheck(dev)
+        if dev.index in _SORT_UNSTABLE:
+            raise RuntimeError("gauc: the in-tree radix sort failed its stability self-check on this device")
+        need = int(h.gauc_workspace_bytes(n, G))
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _chk_vec(ws, torch.uint8, need, "ws", dev)
+        h.gauc(scores=_p(scores), labels=_p(labels), weights=_p(weights), groups=_p(groups), n=n, G=G, out=_p(rec),
+               rec=_p(per), ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(scores))
+        if torch.cuda.is_current_stream_capturing():
+            # (an event recorded into a graph cannot be waited for: the reader synchronises with the replay)
+            return GaucStats(rec, per, weighted, n, G)
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        return GaucStats(rec, per, weighted, n, G, done)
+    _check(ws is None, "gauc: the workspace is a GPU argument")
+    native.cpu().gauc(n=n, G=G, scores=_p(scores), labels=_p(labels), weights=_p(weights), groups=_p(groups),
+                      out=_p(rec), rec=_p(per))
+    return GaucStats(rec, per, weighted, n, G)
+
+
+# ---------------------------------------------------------------------------
 # top-k recommendation: rank a candidate set per query from FM profiles
 # ---------------------------------------------------------------------------
 TOPK_MAX_K = 128

@@ -6,12 +6,16 @@ Reference behaviour kept (run_tffm.py:10-90, :213-231):
 * every ``save_steps``: validation loss ``validation loss at step %d: %.8f`` and
   early stop below ``tolerance`` ("Loss on validation data set is below
   tolerance. Training completed."), checkpoint (CheckpointSaverHook); with ``validation_auc`` (new) also
-  ``validation auc at step %d: %.8f`` and an early stop at ``auc_tolerance``;
+  ``validation auc at step %d: %.8f`` and an early stop at ``auc_tolerance``; with ``validation_gauc`` (new,
+  needs ``validation_group_files``) then ``validation gauc at step %d: %.8f`` -- the grouped AUC of the same
+  forward's scores -- and an early stop at ``gauc_tolerance``;
 * automatic restore of the latest checkpoint in ``log_dir`` (MonitoredTrainingSession);
 * end: ``Average speed:  <ex/s>  ex/s`` and ``Model saved to  <log_dir>``;
 * ``-t FILE``: chrome-trace timeline (reference: first step only; here the
   first few steps after one warm-up step);
-* predict: ``<predict_file>_score`` with one raw score (logit) per line.
+* predict: ``<predict_file>_score`` with one raw score (logit) per line;
+* evaluate (new): loss, ROC AUC and -- with ``predict_group_files`` -- grouped AUC of a checkpoint on the
+  labelled predict files, and ``<predict_file>_gauc`` with one line per group.
 
 Multi-rank runs are synchronous: every step all ranks agree (one tiny
 all-reduce) that each still has a batch, so the run ends cleanly when the first
@@ -32,7 +36,8 @@ from .utils.fault import maybe_inject
 from .utils.trace import roctx_range
 from .data.reader import NativeTextReader, Prefetcher, ReaderState, TextBatchReader, load_file_batch
 from .models.fm import FactorizationMachine
-from .ops.kernels import auc, check_device_errors
+from .data.groups import load_group_files
+from .ops.kernels import auc, check_device_errors, gauc
 from .parallel.dist import DistContext, gather_dealt
 from .utils import checkpoint as ckpt
 from .utils.metrics import MetricsLogger
@@ -67,6 +72,7 @@ class Trainer:
                                           dist=ctx if self.world > 1 else None)
         self.reader_state = ReaderState()
         self.restored_from = None
+        self.val_groups = None  # (this rank's validation group ids, number of groups): load_validation
 
     def close(self) -> None:
         """Release the model's executor resources (graphs, exchange, streams)."""
@@ -141,9 +147,19 @@ class Trainer:
         self.print("Preloading validation data...")
         b = load_file_batch(c.validation_data_files, c.validation_weight_files, c.vocabulary_size,
                             c.hash_feature_id, c.parse_threads)
+        ids = None
+        if c.validation_group_files:
+            # (densified over the whole set before the deal: every rank sees the same ids)
+            gi = load_group_files(c.validation_group_files, c.validation_data_files)
+            if gi.ids.size != b.B:
+                raise ValueError("validation group files have %d lines, validation files %d examples"
+                                 % (gi.ids.size, b.B))
+            ids, num_groups = torch.from_numpy(gi.ids), gi.num_groups
         if self.world > 1:
             idx = torch.arange(self.rank, b.B, self.world)
             b = _take(b, idx)
+            ids = None if ids is None else ids[idx].contiguous()
+        self.val_groups = None if ids is None else (ids.to(self.device), num_groups)
         return b.to(self.device)
 
     def _device_cache(self):
@@ -170,11 +186,24 @@ class Trainer:
         it, the AUC (ops/kernels.py ``auc``, exact and weighted like the loss) over the forward's scores.
         Multi-rank: an exact AUC is no sum of per-rank AUCs, so every rank gathers all ranks' scores,
         labels and weights and computes the same AUC on the full set."""
+        loss, v_auc, _ = self.validation_report(vb)
+        return loss, v_auc
+
+    def validation_report(self, vb, want_auc: bool = True, groups=None) -> tuple:
+        """(loss, ROC AUC or None, ``GaucStats`` or None) of a labelled batch from ONE forward.  ``groups``:
+        ``(this rank's int32 group ids of vb's examples, number of groups)`` for the grouped AUC
+        (ops/kernels.py ``gauc``) of the same scores.  Multi-rank: the ids travel with the scores, labels
+        and weights (as their bit patterns: ``gather_dealt`` moves fp32 vectors and does no arithmetic)."""
         fo = self.model.forward(vb, loss=self.cfg.loss_type)
         loss = self._global_loss(float(fo.loss_sum), vb.B)
-        scores, labels, weights = gather_dealt(self.ctx if self.world > 1 else None,
-                                               [fo.pred[:vb.B].contiguous(), vb.labels, vb.weights])
-        return loss, auc(scores, labels, weights).value()
+        if not want_auc and groups is None:
+            return loss, None, None
+        ids = None if groups is None else groups[0].view(torch.float32)
+        scores, labels, weights, ids = gather_dealt(self.ctx if self.world > 1 else None,
+                                                    [fo.pred[:vb.B].contiguous(), vb.labels, vb.weights, ids])
+        v_auc = auc(scores, labels, weights).value() if want_auc else None
+        st = None if groups is None else gauc(scores, labels, ids.view(torch.int32), groups[1], weights)
+        return loss, v_auc, st
 
     # ------------------------------------------------------------------
     def train(self) -> dict:
@@ -262,7 +291,11 @@ class Trainer:
                 last_loss, tprev = report(pending)
                 pending = None
                 if vb is not None:
-                    if c.validation_auc:
+                    v_gauc = None
+                    if c.validation_gauc:
+                        v_loss, v_auc, gstats = self.validation_report(vb, c.validation_auc, self.val_groups)
+                        v_gauc = gstats.value()
+                    elif c.validation_auc:
                         v_loss, v_auc = self.validation_metrics(vb)
                     else:
                         v_loss, v_auc = self.validation_loss(vb), None
@@ -271,11 +304,17 @@ class Trainer:
                     if v_auc is not None:
                         self.print("validation auc at step %d: %.8f" % (step_num, v_auc))
                         metrics.log(step_num, force=True, validation_auc=v_auc)
+                    if v_gauc is not None:
+                        self.print("validation gauc at step %d: %.8f" % (step_num, v_gauc))
+                        metrics.log(step_num, force=True, validation_gauc=v_gauc)
                     if c.tolerance is not None and v_loss < c.tolerance:
                         self.print("Loss on validation data set is below tolerance. Training completed.")
                         ended_early = True
                     if c.auc_tolerance is not None and v_auc is not None and v_auc >= c.auc_tolerance:
                         self.print("AUC on validation data set is above tolerance. Training completed.")
+                        ended_early = True
+                    if c.gauc_tolerance is not None and v_gauc is not None and v_gauc >= c.gauc_tolerance:
+                        self.print("GAUC on validation data set is above tolerance. Training completed.")
                         ended_early = True
                 check_device_errors(self.device)  # (kernels' sticky error word: fail before saving)
                 if c.log_dir:
@@ -336,6 +375,47 @@ class Trainer:
                 written.append(out)
         self.print("Done. Scores saved to same directory as predict files")
         return written
+
+    # ------------------------------------------------------------------
+    def evaluate(self) -> dict:
+        """``run.py evaluate``: loss and ROC AUC of the restored model on every (labelled) predict file, from
+        one forward with unit weights, printed as ``evaluate <file>: examples N loss L auc A``.  With ``[Predict]
+        predict_group_files`` the line goes on `` gauc G valid_groups V/T coverage C`` and ``<file>_gauc`` gets
+        one line per group, ``key auc positives negatives examples``, by ascending AUC then key; the groups
+        without a positive or without a negative follow, by key, with ``nan``.  Returns the metrics per file.
+        Multi-rank runs deal the examples as ``predict`` does; rank 0 writes."""
+        c = self.cfg
+        if not self.restore():
+            raise FileNotFoundError(f"no checkpoint found in {c.log_dir}")
+        self.print("========", "evaluate", "========")
+        results = {}
+        for k, path in enumerate(c.predict_files):
+            b = load_file_batch([path], None, c.vocabulary_size, c.hash_feature_id, c.parse_threads)
+            gi = ids = None
+            if c.predict_group_files:
+                gi = load_group_files([c.predict_group_files[k]], [path])
+                if gi.ids.size != b.B:
+                    raise ValueError(f"{c.predict_group_files[k]}: {gi.ids.size} lines but {path} has {b.B} examples")
+                ids = torch.from_numpy(gi.ids)
+            mine = b
+            if self.world > 1:
+                idx = torch.arange(self.rank, b.B, self.world)
+                mine = _take(b, idx)
+                ids = None if ids is None else ids[idx].contiguous()
+            groups = None if ids is None else (ids.to(self.device), gi.num_groups)
+            loss, v_auc, st = self.validation_report(mine.to(self.device), True, groups)
+            res = {"examples": b.B, "loss": loss, "auc": v_auc}
+            line = "evaluate %s: examples %d loss %.8f auc %.8f" % (path, b.B, loss, v_auc)
+            if st is not None:
+                res.update(gauc=st.value(), valid_groups=st.valid_groups(), groups=gi.num_groups,
+                           coverage=st.coverage())
+                line += " gauc %.8f valid_groups %d/%d coverage %.8f" % (res["gauc"], res["valid_groups"],
+                                                                        gi.num_groups, res["coverage"])
+                if self.rank == 0:
+                    res["gauc_file"] = _write_group_aucs(path + "_gauc", gi, st.per_group().cpu().tolist())
+            self.print(line)
+            results[path] = res
+        return results
 
 
     # ------------------------------------------------------------------
@@ -463,6 +543,20 @@ class Trainer:
             written.append(out)
         self.print("Done. Recommendations saved to same directory as predict files")
         return written
+
+
+def _write_group_aucs(out: str, gi, recs: list) -> str:
+    """``<file>_gauc`` of ``Trainer.evaluate`` from the per-group ``[U2, P, N]`` records."""
+    sizes = np.bincount(gi.ids, minlength=gi.num_groups)
+    rows = []
+    for g, (u2, p, n) in enumerate(recs):
+        valid = p > 0 and n > 0
+        rows.append((not valid, u2 / (2 * p * n) if valid else 0.0, gi.keys[g], g))
+    with open(out, "w") as f:
+        for invalid, a, key, g in sorted(rows):
+            f.write("%s %s %s %s %d\n" % (key, "nan" if invalid else str(np.float32(a)), recs[g][1], recs[g][2],
+                                          sizes[g]))
+    return out
 
 
 RECOMMEND_PROFILE_BATCH = 65536  # candidate lines per forward pass of ``Trainer.recommend``
