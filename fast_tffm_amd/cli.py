@@ -1,5 +1,6 @@
 """Command line:
-``python run.py {train,predict,evaluate,explain,recommend,generate,convert,import_tf,export_tf} CONFIG [options]``.
+``python run.py {train,predict,evaluate,calibrate,explain,recommend,generate,convert,import_tf,export_tf} CONFIG
+[options]``.
 
 Same arguments as the reference's run_tffm.py (run_tffm.py:124-162):
   task {train,predict,generate}, config_file,
@@ -12,7 +13,10 @@ Extensions: --device {auto,cpu,cuda}, --mode {auto,local,shard,dp,dp_dense},
 ``recommend CONFIG --candidates FILE [--top N]`` (for every line of the predict files the N best lines of
 FILE by the score of both taken together: ``<file>_recommend``, trainer.Trainer.recommend), the task
 ``evaluate CONFIG`` (loss and ROC AUC of the checkpoint on the labelled predict files and, with ``[Predict]
-predict_group_files``, the grouped AUC and ``<file>_gauc``: trainer.Trainer.evaluate), and the task
+predict_group_files``, the grouped AUC and ``<file>_gauc``: trainer.Trainer.evaluate), the task ``calibrate
+CONFIG`` (an exact isotonic fit of the checkpoint's scores on ``[Train] validation_files``, written as
+``calibration.json`` into the checkpoint's directory: trainer.Trainer.calibrate; ``predict CONFIG --calibrated``
+then also writes ``<file>_prob``), and the task
 ``convert CONFIG --out DIR``: parse the config's train files (+ weight files) once
 into binary CSR caches (``DIR/<name>.fmb``, data/bincache.py) that ``train``
 reads at memory speed when ``train_files`` points at them.  Checkpoint migration:
@@ -38,8 +42,8 @@ import sys
 
 def build_parser() -> argparse.ArgumentParser:
     p = argparse.ArgumentParser(prog="run.py", description="MI355X-native distributed factorization machine")
-    p.add_argument("task", choices=["train", "predict", "evaluate", "explain", "recommend", "generate", "convert",
-                                    "import_tf", "export_tf"])
+    p.add_argument("task", choices=["train", "predict", "evaluate", "calibrate", "explain", "recommend", "generate",
+                                    "convert", "import_tf", "export_tf"])
     p.add_argument("config_file", type=str)
     p.add_argument("--dist", nargs=4, metavar=("JOB_NAME", "TASK_INDEX", "PS_HOSTS", "WORKER_HOSTS"), default=None,
                    help="For distributed training or prediction")
@@ -61,6 +65,9 @@ def build_parser() -> argparse.ArgumentParser:
                         "recommend: candidates per line (1..128, default 10)")
     p.add_argument("--candidates", default=None, metavar="FILE",
                    help="recommend: the candidates, one per line in the predict files' format")
+    p.add_argument("--calibrated", action="store_true",
+                   help="predict: also write <file>_prob, the calibrated probability of every score (needs the "
+                        "calibration.json that 'calibrate' wrote into the checkpoint's directory)")
     p.add_argument("--tf_checkpoint", default=None,
                    help="import_tf: TF checkpoint directory (its 'checkpoint' file names the newest) or prefix")
     return p
@@ -94,7 +101,7 @@ def main(argv: list[str] | None = None) -> int:
         # queues (HIP's default 4 makes them share and serialize); before HIP starts
         fmdist.ensure_hw_queues()
 
-    if args.task in ("predict", "evaluate", "explain", "recommend") and cfg.log_dir is None:
+    if args.task in ("predict", "evaluate", "calibrate", "explain", "recommend") and cfg.log_dir is None:
         print("Missing log directory. Must include a checkpoint file.")
         os._exit(1)
     if args.task == "generate":
@@ -142,18 +149,25 @@ def main(argv: list[str] | None = None) -> int:
             print(f"All {ctx.world} workers joined (wait-for-workers={args.wait_for_workers}).")
     from .trainer import Trainer
 
+    from .calibration import CalibrationError
+
     tr = Trainer(cfg, ctx, monitor=args.monitor, trace=args.trace)
     try:
         if args.task == "train":
             tr.train()
         elif args.task == "evaluate":
             tr.evaluate()
+        elif args.task == "calibrate":
+            tr.calibrate()
         elif args.task == "explain":
             tr.explain(top=args.top)
         elif args.task == "recommend":
             tr.recommend(args.candidates, top=10 if args.top is None else args.top)
         else:
-            tr.predict()
+            tr.predict(calibrated=args.calibrated)
+    except CalibrationError as e:
+        print(e)
+        return 1
     finally:
         tr.close()
         if ctx is not None:

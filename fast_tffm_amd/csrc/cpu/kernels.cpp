@@ -9,6 +9,7 @@
 #include <omp.h>
 
 #include "../hash64.h"
+#include "../iso_hull.h"
 #include "../topk_order.h"
 
 namespace fm {
@@ -399,6 +400,110 @@ void gauc(int n, long long G, const float* scores, const float* labels, const fl
   std::sort(kv.begin(), kv.end());
   if (weights) gauc_pass<double>(kv, G, labels, weights, nans, out, static_cast<double*>(rec));
   else gauc_pass<uint64_t>(kv, G, labels, weights, nans, out, static_cast<uint64_t*>(rec));
+}
+
+namespace {
+template <typename T>
+void isotonic_pass(const std::vector<uint64_t>& kv, const float* labels, const float* weights, uint64_t nans,
+                   float* lo, float* hi, T* W, T* Y, double* v, double* fitted, T* out, int tile) {
+  const int n = static_cast<int>(kv.size());
+  std::vector<T> cW(n + 1), cY(n + 1);
+  std::vector<uint8_t> cand(n + 1);
+  T w = 0, y = 0;
+  for (int j = 0; j < n; ++j) {
+    const uint32_t i = static_cast<uint32_t>(kv[j]);
+    const T wi = weights ? static_cast<T>(weights[i]) : static_cast<T>(1);
+    cW[j] = w;
+    cY[j] = y;
+    cand[j] = j == 0 || (kv[j - 1] >> 32) != (kv[j] >> 32);
+    w += wi;
+    if (labels[i] > 0.f) y += wi;
+  }
+  cW[n] = w;
+  cY[n] = y;
+  cand[n] = 1;
+  std::vector<int> H(n + 1);
+  int c = 0;
+  if (tile < 2) {
+    c = iso::leaf_hull<T>(cW.data(), cY.data(), cand.data(), n + 1, H.data());
+  } else {
+    const iso::Diagram<T> d{cW.data(), cY.data(), n};
+    const int ntl = n / tile + 1;
+    std::vector<int> A(static_cast<size_t>(ntl) * tile), B(A.size()), ca(ntl), cb(ntl);
+    for (int t = 0; t < ntl; ++t) {
+      const int base = t * tile, cnt = std::min(tile, n + 1 - base);
+      ca[t] = iso::leaf_hull<T>(cW.data() + base, cY.data() + base, cand.data() + base, cnt, A.data() + base);
+      for (int k = 0; k < ca[t]; ++k) A[base + k] += base;
+    }
+    int *src = A.data(), *dst = B.data(), *sc = ca.data(), *dc = cb.data();
+    for (int level = 0; (1ll << level) < ntl; ++level) {
+      for (long long k = 0; ((2 * k) << level) < ntl; ++k) {
+        const long long tl = (2 * k) << level, tr = (2 * k + 1) << level;
+        const int* L = src + tl * tile;
+        const int nL = sc[tl];
+        int nR = 0, a = nL - 1, b = 0;
+        const int* R = L;
+        if (tr < ntl) {
+          R = src + tr * tile;
+          nR = sc[tr];
+          if (nL > 0 && nR > 0) iso::bridge<T>(d, L, nL, R, nR, a, b);
+        }
+        int* D = dst + tl * tile;
+        std::copy(L, L + a + 1, D);
+        std::copy(R + b, R + nR, D + a + 1);
+        dc[tl] = a + 1 + nR - b;
+      }
+      std::swap(src, dst);
+      std::swap(sc, dc);
+    }
+    c = sc[0];
+    std::copy(src, src + c, H.begin());
+  }
+  const int m = c - 1;  // (H[0] = 0, H[m] = n)
+  for (int b = 0; b < m; ++b) {
+    const int p = H[b], q = H[b + 1];
+    const uint32_t bl = iso::key_to_bits(static_cast<uint32_t>(kv[p] >> 32));
+    const uint32_t bh = iso::key_to_bits(static_cast<uint32_t>(kv[q - 1] >> 32));
+    std::memcpy(lo + b, &bl, 4);
+    std::memcpy(hi + b, &bh, 4);
+    W[b] = cW[q] - cW[p];
+    Y[b] = cY[q] - cY[p];
+    v[b] = static_cast<double>(Y[b]) / static_cast<double>(W[b]);
+    if (fitted)
+      for (int j = p; j < q; ++j) fitted[static_cast<uint32_t>(kv[j])] = v[b];
+  }
+  out[0] = static_cast<T>(m);
+  out[1] = w;
+  out[2] = y;
+  out[3] = static_cast<T>(nans);
+  out[4] = 0;
+}
+}  // namespace
+
+void isotonic(int n, const float* scores, const float* labels, const float* weights, float* lo, float* hi, void* W,
+              void* Y, double* v, double* fitted, void* out, int tile) {
+  std::vector<uint64_t> kv(n > 0 ? n : 0);
+  uint64_t nans = 0;
+  for (int j = 0; j < n; ++j) {
+    uint32_t b;
+    std::memcpy(&b, scores + j, 4);
+    nans += (b & 0x7fffffffu) > 0x7f800000u;
+    if (b == 0x80000000u) b = 0u;
+    const uint32_t key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+    kv[j] = (static_cast<uint64_t>(key) << 32) | static_cast<uint32_t>(j);
+  }
+  std::sort(kv.begin(), kv.end());
+  if (weights)
+    isotonic_pass<double>(kv, labels, weights, nans, lo, hi, static_cast<double*>(W), static_cast<double*>(Y), v,
+                          fitted, static_cast<double*>(out), tile);
+  else
+    isotonic_pass<uint64_t>(kv, labels, weights, nans, lo, hi, static_cast<uint64_t*>(W), static_cast<uint64_t*>(Y),
+                            v, fitted, static_cast<uint64_t*>(out), tile);
+}
+
+void calib_apply(long long n, const float* scores, const float* x, const float* y, int m2, float* out) {
+  for (long long i = 0; i < n; ++i)
+    out[i] = iso::calib_value(scores[i], x, y, m2, [](float t, float d, float v) { return std::fmaf(t, d, v); });
 }
 
 void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q_stride, const float* C,

@@ -65,6 +65,18 @@ void auc(int n, const float* scores, const float* labels, const float* weights, 
 void gauc(int n, long long G, const float* scores, const float* labels, const float* weights, const int* groups,
           void* out, void* rec);
 
+// Exact isotonic regression (hip/isotonic.hip: same definition, same two modes) of n >= 1 scores, weights null
+// or all > 0: the blocks' first / last score lo, hi, weight W, positive weight Y (uint64 when weights is null,
+// else fp64 summed in sorted order) and value v = Y / W (fp64), [n] each; out[5] = blocks, total weight, positive
+// weight, NaN scores, 0; fitted[n] (fp64, input order) unless null.  tile == 0: the serial stack; tile >= 2: the
+// GPU's formulation, hulls of tiles of that many points merged pairwise by their bridges (the same vertex list).
+void isotonic(int n, const float* scores, const float* labels, const float* weights, float* lo, float* hi, void* W,
+              void* Y, double* v, double* fitted, void* out, int tile);
+
+// out[i] = the calibrated probability of scores[i] from the thresholds x[m2] = lo_0, hi_0, lo_1, hi_1, ... and
+// the values y[m2] = v_0, v_0, v_1, v_1, ... (hip/isotonic.hip calib_apply_kernel: the same formula).
+void calib_apply(long long n, const float* scores, const float* x, const float* y, int m2, float* out);
+
 // Counter-based U(-range, range) init, identical to the gfx950 init_rows kernel.
 void init_rows(void* v, long long v_stride, float* w, long long w_stride, long long rows, int K, int Kp, int dtype,
                long long gid_mul, long long gid_add, unsigned long long seed, float range, int threads);

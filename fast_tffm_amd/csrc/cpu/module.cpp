@@ -482,4 +482,25 @@ PYBIND11_MODULE(_fm_cpu, m) {
       },
       py::arg("n"), py::arg("G"), py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("groups"),
       py::arg("out"), py::arg("rec"));
+
+  m.def(
+      "isotonic",
+      [](int n, u64 scores, u64 labels, u64 weights, u64 lo, u64 hi, u64 W, u64 Y, u64 v, u64 fitted, u64 out,
+         int tile) {
+        if (n < 1 || tile == 1 || tile < 0) throw std::invalid_argument("isotonic: n >= 1, tile 0 or >= 2");
+        py::gil_scoped_release nogil;
+        fm::cpu::isotonic(n, P<const float>(scores), P<const float>(labels), P<const float>(weights), P<float>(lo),
+                          P<float>(hi), P<void>(W), P<void>(Y), P<double>(v), P<double>(fitted), P<void>(out), tile);
+      },
+      py::arg("n"), py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("lo"), py::arg("hi"),
+      py::arg("W"), py::arg("Y"), py::arg("v"), py::arg("fitted"), py::arg("out"), py::arg("tile") = 0);
+
+  m.def(
+      "calib_apply",
+      [](long long n, u64 scores, u64 x, u64 y, int m2, u64 out) {
+        if (n < 0 || m2 < 2 || (m2 & 1)) throw std::invalid_argument("calib_apply: n >= 0, m2 even and >= 2");
+        py::gil_scoped_release nogil;
+        fm::cpu::calib_apply(n, P<const float>(scores), P<const float>(x), P<const float>(y), m2, P<float>(out));
+      },
+      py::arg("n"), py::arg("scores"), py::arg("x"), py::arg("y"), py::arg("m2"), py::arg("out"));
 }

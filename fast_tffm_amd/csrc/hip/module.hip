@@ -27,6 +27,7 @@ using u64 = std::uintptr_t;
 #include "fm_topk.hip"
 #include "dedup.hip"
 #include "auc.hip"
+#include "isotonic.hip"
 #include "gauc.hip"
 #include "shard.hip"
 #include "init.hip"
@@ -315,6 +316,43 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       },
       py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("n"), py::arg("out"), py::arg("ws"),
       py::arg("ws_bytes"), py::arg("stream"));
+
+  m.def(
+      "isotonic_workspace_bytes",
+      [](long long n) {
+        const size_t b = fm::isotonic_workspace_bytes(n);
+        if (!b) throw std::invalid_argument("isotonic: n must be in [0, 2^30)");
+        return b;
+      },
+      py::arg("n"));
+  m.def(
+      "isotonic_block_offsets",  // byte offsets of the block arrays (lo, hi, W, Y, v) in the workspace
+      [](long long n) {
+        if (n < 1 || !fm::isotonic_workspace_bytes(n)) throw std::invalid_argument("isotonic: n must be in [1, 2^30)");
+        size_t off[5];
+        fm::isotonic_block_offsets((int)n, off);
+        return std::vector<size_t>(off, off + 5);
+      },
+      py::arg("n"));
+  m.def(
+      "isotonic",  // isotonic fit: record [blocks, W, Y, nan count, sort error word] into out[5] (int64 when
+                   // weights == 0, else fp64), block arrays into ws, fitted[n] (fp64) when not 0; asynchronous
+                   // (ops/kernels.py IsotonicFit)
+      [](u64 scores, u64 labels, u64 weights, int n, u64 fitted, u64 out, u64 ws, size_t ws_bytes, u64 stream) {
+        check(fm::launch_isotonic(P<const float>(scores), P<const float>(labels), P<const float>(weights), n,
+                                  P<double>(fitted), P<void>(out), P<void>(ws), ws_bytes, S(stream)),
+              "isotonic");
+      },
+      py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("n"), py::arg("fitted"), py::arg("out"),
+      py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
+  m.def(
+      "calib_apply",  // out[i] = calibrated probability of scores[i] (thresholds x[m2], values y[m2])
+      [](u64 scores, int n, u64 x, u64 y, int m2, u64 out, u64 stream) {
+        check(fm::launch_calib_apply(P<const float>(scores), n, P<const float>(x), P<const float>(y), m2,
+                                     P<float>(out), S(stream)),
+              "calib_apply");
+      },
+      py::arg("scores"), py::arg("n"), py::arg("x"), py::arg("y"), py::arg("m2"), py::arg("out"), py::arg("stream"));
 
   m.def(
       "gauc_workspace_bytes",

@@ -1054,6 +1054,178 @@ def gauc(scores: torch.Tensor, labels: torch.Tensor, groups: torch.Tensor, num_g
 
 
 # ---------------------------------------------------------------------------
+# calibration: exact isotonic regression of (score, label, weight)
+# ---------------------------------------------------------------------------
+class IsotonicFit:
+    """The record of one ``isotonic_fit`` call, on the op's device: ``[blocks, total weight, positive weight,
+    NaN scores, sort error word]`` -- int64 (unweighted: exact) or float64 (weighted) -- and the block arrays.
+    The readers (``count`` / ``totals`` / ``blocks`` / ``fitted`` / ``calibrator``) read the record (a host
+    sync on the GPU) and raise when a score is NaN (there is no fit then) or when the GPU sort reported a
+    failed look-back.  On the GPU the block arrays live in the call's workspace: read them before the
+    workspace is used again (``blocks`` copies)."""
+
+    __slots__ = ("rec", "weighted", "n", "done", "arrays", "fit", "keep", "scores", "_head")
+
+    def __init__(self, rec: torch.Tensor, weighted: bool, n: int, arrays: tuple | None = None,
+                 fit: torch.Tensor | None = None, done: "torch.cuda.Event | None" = None,
+                 keep: torch.Tensor | None = None, scores: torch.Tensor | None = None):
+        self.rec, self.weighted, self.n, self.arrays, self.fit, self.done = rec, weighted, n, arrays, fit, done
+        self.keep, self.scores = keep, scores  # zero-weight examples were dropped: the mask, every score
+        self._head = None
+
+    def _read(self) -> tuple:
+        if self._head is None:
+            if self.done is not None:
+                self.done.synchronize()
+            m, w, y, nans, err = self.rec.tolist()
+            if err:
+                raise RuntimeError(f"isotonic_fit: the radix sort's look-back spin bound was hit (error word "
+                                   f"{int(err)}); no fit for this input")
+            if nans:
+                raise ValueError(f"isotonic_fit: {int(nans)} NaN score(s); there is no fit")
+            self._head = (int(m), w, y)
+        return self._head
+
+    def count(self) -> int:
+        """Number of blocks (0: no example with weight)."""
+        return self._read()[0]
+
+    def totals(self) -> tuple:
+        """(total weight, positive weight): Python ints (unweighted) or floats."""
+        return self._read()[1:]
+
+    def blocks(self) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """(lo, hi, weight, positives, value) of the blocks in ascending score order: the fp32 scores of a
+        block's first / last example, its weight and positive weight (int64 / float64) and value (float64,
+        strictly increasing)."""
+        m = self.count()
+        if self.arrays is None or m == 0:
+            dt = torch.float64 if self.weighted else torch.int64
+            dev = self.rec.device
+            return (torch.empty(0, dtype=torch.float32, device=dev), torch.empty(0, dtype=torch.float32, device=dev),
+                    torch.empty(0, dtype=dt, device=dev), torch.empty(0, dtype=dt, device=dev),
+                    torch.empty(0, dtype=torch.float64, device=dev))
+        return tuple(a[:m].clone() for a in self.arrays)
+
+    def calibrator(self) -> tuple[torch.Tensor, torch.Tensor]:
+        """The fp32 threshold list ``x = [lo_0, hi_0, lo_1, hi_1, ...]`` and ``y = [v_0, v_0, v_1, v_1, ...]``
+        (``calibrate_apply``'s arguments), on the op's device."""
+        lo, hi, _, _, v = self.blocks()
+        _check(lo.numel() > 0, "isotonic_fit: no example with weight, so no calibrator")
+        v32 = v.to(torch.float32)
+        return torch.stack((lo, hi), dim=1).reshape(-1).contiguous(), torch.stack((v32, v32), dim=1).reshape(-1)
+
+    def fitted(self) -> torch.Tensor:
+        """The fitted value of every example in input order (float64; needs ``want_fitted``).  An example that
+        was dropped for its zero weight gets the calibrator's value at its score."""
+        _check(self.fit is not None, "isotonic_fit: fitted values need want_fitted=True")
+        m = self.count()
+        if self.keep is None:
+            return self.fit
+        out = torch.full((self.keep.numel(),), float("nan"), dtype=torch.float64, device=self.keep.device)
+        if m:
+            out[self.keep] = self.fit
+            x, y = self.calibrator()
+            out[~self.keep] = calibrate_apply(self.scores[~self.keep].contiguous(), x, y).to(torch.float64)
+        return out
+
+
+def isotonic_workspace(n: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of ``isotonic_fit`` for up to ``n`` scores (GPU)."""
+    return torch.empty(int(native.hip().isotonic_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def isotonic_fit(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None = None, *,
+                 want_fitted: bool = False, ws: torch.Tensor | None = None, _cpu_tile: int = 0) -> IsotonicFit:
+    """Exact isotonic regression: the non-decreasing map from raw score to P(positive) with the least weighted
+    squared error (equally: the least log loss) on these examples.
+
+    ``auc``'s conventions: an example is positive iff ``label > 0``, ``weights`` None = all ones, scores compare
+    as IEEE fp32 values (-0.0 == +0.0, infinities and denormals ordered as usual), NaN scores are counted and
+    make the readers raise.  With the examples sorted by score, the fit is the slope of the lower convex hull of
+    the cumulative (weight, positive weight) diagram over the ends of the runs of tied scores, with the minimal
+    vertex set; consecutive vertices bound a block of examples that share one value ``positives / weight``.
+    Unweighted fits are integers (exact, the same on GPU and CPU); weighted ones are fp64 in a fixed order
+    (bitwise the same run to run).  Examples with weight 0 are dropped here (the kernels need ``w > 0``: one host
+    read of the weights' signs, so a weighted fit is no step of a captured graph).
+    GPU: hip/isotonic.hip on the current stream (``ws``: reusable ``isotonic_workspace``); CPU: a sort and the
+    serial stack.  ``n == 0`` or no weight at all launches nothing and has no blocks.
+    """
+    dev = scores.device
+    n = scores.numel()
+    _chk_vec(scores, torch.float32, n, "scores", dev)
+    _chk_vec(labels, torch.float32, n, "labels", dev)
+    _chk_vec(weights, torch.float32, n, "weights", dev)
+    _check(labels.numel() == n and (weights is None or weights.numel() == n),
+           "isotonic_fit: one label / weight per score")
+    _check(n < 2**30, "isotonic_fit: n must be < 2^30 (the radix sort's bound)")
+    weighted = weights is not None
+    keep = all_scores = None
+    if weighted and n > 0:
+        _check(bool((weights >= 0).all()), "weights: must be >= 0")  # (NaN weights fail too)
+        pos = weights > 0
+        if not bool(pos.all()):
+            keep, all_scores = pos, scores
+            scores, labels, weights = scores[pos].contiguous(), labels[pos].contiguous(), weights[pos].contiguous()
+            n = scores.numel()
+    rdt = torch.float64 if weighted else torch.int64
+    if n == 0:  # (a host record: nothing is launched)
+        fit = torch.empty(0, dtype=torch.float64, device=dev) if want_fitted else None
+        return IsotonicFit(torch.zeros(5, dtype=rdt), weighted, 0, None, fit, None, keep, all_scores)
+    rec = torch.empty(5, dtype=rdt, device=dev)
+    fit = torch.empty(n, dtype=torch.float64, device=dev) if want_fitted else None
+    if _is_gpu(scores):
+        h = native.hip()
+        _sort_selfcheck(dev)
+        if dev.index in _SORT_UNSTABLE:
+            raise RuntimeError("isotonic_fit: the in-tree radix sort failed its stability self-check on this device")
+        need = int(h.isotonic_workspace_bytes(n))
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _chk_vec(ws, torch.uint8, need, "ws", dev)
+        h.isotonic(scores=_p(scores), labels=_p(labels), weights=_p(weights), n=n, fitted=_p(fit), out=_p(rec),
+                   ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(scores))
+        done = torch.cuda.Event()
+        done.record(torch.cuda.current_stream(dev))
+        off = h.isotonic_block_offsets(n)
+        dts = (torch.float32, torch.float32, rdt, rdt, torch.float64)
+        arrays = tuple(ws[o:o + n * d.itemsize].view(d) for o, d in zip(off, dts))
+        return IsotonicFit(rec, weighted, n, arrays, fit, done, keep, all_scores)
+    _check(ws is None, "isotonic_fit: the workspace is a GPU argument")
+    arrays = (torch.empty(n, dtype=torch.float32), torch.empty(n, dtype=torch.float32), torch.empty(n, dtype=rdt),
+              torch.empty(n, dtype=rdt), torch.empty(n, dtype=torch.float64))
+    native.cpu().isotonic(n=n, scores=_p(scores), labels=_p(labels), weights=_p(weights), lo=_p(arrays[0]),
+                          hi=_p(arrays[1]), W=_p(arrays[2]), Y=_p(arrays[3]), v=_p(arrays[4]), fitted=_p(fit),
+                          out=_p(rec), tile=int(_cpu_tile))
+    return IsotonicFit(rec, weighted, n, arrays, fit, None, keep, all_scores)
+
+
+def calibrate_apply(scores: torch.Tensor, x: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """Calibrated probabilities of raw scores from a fit's thresholds ``x = [lo_0, hi_0, lo_1, hi_1, ...]`` and
+    values ``y = [v_0, v_0, v_1, v_1, ...]`` (fp32, ``IsotonicFit.calibrator``): NaN for NaN; the first / last
+    block's value at and beyond the ends; exactly ``v_b`` for ``lo_b <= s <= hi_b``; between two blocks
+    ``fmaf(t, v_{b+1} - v_b, v_b)`` with ``t = (s - hi_b) / (lo_{b+1} - hi_b)``, clamped into ``[v_b, v_{b+1}]``
+    (``t`` = 0 / 1 / 0.5 when the gap's upper / lower / both ends are infinite).  Monotone in the score.
+    GPU: hip/isotonic.hip calib_apply_kernel on the current stream; CPU: the same formula."""
+    dev = scores.device
+    n = scores.numel()
+    m2 = x.numel()
+    _chk_vec(scores, torch.float32, n, "scores", dev)
+    _chk_vec(x, torch.float32, m2, "x", dev)
+    _chk_vec(y, torch.float32, m2, "y", dev)
+    _check(m2 >= 2 and m2 % 2 == 0 and y.numel() == m2, "calibrate_apply: x, y hold two entries per block")
+    out = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    if _is_gpu(scores):
+        native.hip().calib_apply(scores=_p(scores), n=n, x=_p(x), y=_p(y), m2=m2, out=_p(out),
+                                 stream=_stream(scores))
+    else:
+        native.cpu().calib_apply(n=n, scores=_p(scores), x=_p(x), y=_p(y), m2=m2, out=_p(out))
+    return out
+
+
+# ---------------------------------------------------------------------------
 # top-k recommendation: rank a candidate set per query from FM profiles
 # ---------------------------------------------------------------------------
 TOPK_MAX_K = 128

@@ -14,6 +14,7 @@ Here the export directory holds both forms::
     export_path/variables/variables.{index,data-*}  its variables (TF V2 tensor bundle)
     export_path/saved_model.json                    signature + model metadata (native predictor)
     export_path/variables/vocab_block_{i}.npy       reference layout [V // N + 1, K + 1]
+    export_path/calibration.json                    the checkpoint's calibrator, when ``run.py calibrate`` wrote one
 
 (utils/saved_model.py writes the SavedModel without TensorFlow; its parity with TF's loader
 is unpinned, checked by an independent numpy interpreter of the graph in the tests.)
@@ -29,10 +30,13 @@ from __future__ import annotations
 import argparse
 import json
 import os
+import shutil
 import sys
 
 import numpy as np
 import torch
+
+from .calibration import FILE_NAME as CALIBRATION_FILE, Calibrator
 
 SIGNATURE = {
     "tag_set": "serve",
@@ -75,6 +79,8 @@ def export_model(ckpt_dir: str, export_path: str, *, vocabulary_block_num: int, 
               for i in range(vocabulary_block_num)]
     write_saved_model(tmp, blocks, meta["vocabulary_size"], meta["factor_num"], global_bias=meta.get("global_bias"))
     del blocks
+    if os.path.exists(os.path.join(ckpt_dir, CALIBRATION_FILE)):
+        shutil.copyfile(os.path.join(ckpt_dir, CALIBRATION_FILE), os.path.join(tmp, CALIBRATION_FILE))
     os.replace(tmp, export_path)
     return export_path
 
@@ -106,8 +112,10 @@ def parse_serving_lines(lines, vocab_size: int, hash_feature_id: bool = False, t
 class ServingModel:
     """Loaded serving export: ``predict(data_lines) -> scores``."""
 
-    def __init__(self, meta: dict, v: torch.Tensor, w: torch.Tensor, device: torch.device):
+    def __init__(self, meta: dict, v: torch.Tensor, w: torch.Tensor, device: torch.device,
+                 calibrator: Calibrator | None = None):
         self.meta, self.v, self.w, self.device = meta, v, w, device
+        self.calibrator = calibrator  # the export's calibration.json, or None
         self.K = meta["factor_num"]
         self.Kp = v.shape[1]
 
@@ -130,7 +138,9 @@ class ServingModel:
             rows = torch.from_numpy(np.ascontiguousarray(blk[(sel // N).numpy()]))
             w[sel] = rows[:, 0]
             v[sel, :K] = rows[:, 1:]
-        return cls(meta, v.to(dev), w.to(dev), dev)
+        cal_path = os.path.join(export_path, CALIBRATION_FILE)
+        cal = Calibrator.load(cal_path) if os.path.exists(cal_path) else None
+        return cls(meta, v.to(dev), w.to(dev), dev, cal)
 
     def _parse_gpu(self, flat: list):
         """GPU tokenizer (hip/parse.hip) over the lines behind a dummy label, ':value' required;
@@ -170,6 +180,18 @@ class ServingModel:
         offsets, ids, vals, bias = self._parse(data_lines)
         fo = Kn.fm_forward(offsets, ids, vals, self.v, self.w, self.Kp, want_r1=False, bias=bias)
         return fo.pred.cpu().numpy()
+
+    def predict_proba(self, data_lines) -> np.ndarray:
+        """Calibrated probabilities of the lines: ``predict``'s raw scores through the export's calibrator
+        (``run.py calibrate`` before ``generate``); raises when the export has none."""
+        from .ops import kernels as Kn
+
+        if self.calibrator is None:
+            raise RuntimeError("this export has no calibration.json: run 'calibrate' on the checkpoint, then "
+                               "'generate' again")
+        offsets, ids, vals, bias = self._parse(data_lines)
+        fo = Kn.fm_forward(offsets, ids, vals, self.v, self.w, self.Kp, want_r1=False, bias=bias)
+        return self.calibrator(fo.pred[:offsets.numel() - 1]).cpu().numpy()
 
     def explain(self, data_lines) -> tuple[np.ndarray, np.ndarray, np.ndarray, np.ndarray]:
         """``(scores [B], offsets [B + 1], ids [nnz], contrib [nnz])``: the lines parsed as ``predict`` parses

@@ -15,7 +15,10 @@ Reference behaviour kept (run_tffm.py:10-90, :213-231):
   first few steps after one warm-up step);
 * predict: ``<predict_file>_score`` with one raw score (logit) per line;
 * evaluate (new): loss, ROC AUC and -- with ``predict_group_files`` -- grouped AUC of a checkpoint on the
-  labelled predict files, and ``<predict_file>_gauc`` with one line per group.
+  labelled predict files, and ``<predict_file>_gauc`` with one line per group;
+* calibrate (new): an exact isotonic fit of the checkpoint's scores on the validation files, written as
+  ``calibration.json`` into the checkpoint's directory; ``predict --calibrated`` then also writes
+  ``<predict_file>_prob`` with one calibrated probability per line.
 
 Multi-rank runs are synchronous: every step all ranks agree (one tiny
 all-reduce) that each still has a batch, so the run ends cleanly when the first
@@ -37,7 +40,8 @@ from .utils.trace import roctx_range
 from .data.reader import NativeTextReader, Prefetcher, ReaderState, TextBatchReader, load_file_batch
 from .models.fm import FactorizationMachine
 from .data.groups import load_group_files
-from .ops.kernels import auc, check_device_errors, gauc
+from .calibration import FILE_NAME as CALIBRATION_FILE, CalibrationError, Calibrator, log_loss_sum_of_blocks
+from .ops.kernels import auc, check_device_errors, gauc, isotonic_fit
 from .parallel.dist import DistContext, gather_dealt
 from .utils import checkpoint as ckpt
 from .utils.metrics import MetricsLogger
@@ -347,10 +351,20 @@ class Trainer:
                 "last_loss": last_loss, "early_stop": ended_early}
 
     # ------------------------------------------------------------------
-    def predict(self) -> list[str]:
+    def predict(self, calibrated: bool = False) -> list[str]:
+        """``run.py predict``: ``<file>_score`` with one raw score per line.  ``calibrated``: also
+        ``<file>_prob`` with the calibrated probability of every score, from the ``calibration.json`` that
+        ``calibrate`` wrote into the restored checkpoint's directory."""
         c = self.cfg
         if not self.restore():
             raise FileNotFoundError(f"no checkpoint found in {c.log_dir}")
+        cal = None
+        if calibrated:
+            cal_path = os.path.join(self.restored_from, CALIBRATION_FILE)
+            if not os.path.exists(cal_path):
+                raise CalibrationError(f"predict --calibrated: no {CALIBRATION_FILE} in {self.restored_from}; run "
+                                       "'calibrate' on this checkpoint first")
+            cal = Calibrator.load(cal_path)
         self.print("========", "predict", "========")
         written = []
         for path in c.predict_files:
@@ -373,8 +387,69 @@ class Trainer:
                     for s in scores:
                         f.write(str(np.float32(s)) + "\n")
                 written.append(out)
+                if cal is not None:
+                    probs = cal(torch.from_numpy(np.ascontiguousarray(scores, np.float32)).to(self.device))
+                    with open(path + "_prob", "w") as f:
+                        for p in probs.cpu().numpy():
+                            f.write(str(np.float32(p)) + "\n")
+                    written.append(path + "_prob")
         self.print("Done. Scores saved to same directory as predict files")
         return written
+
+    # ------------------------------------------------------------------
+    def calibrate(self) -> dict:
+        """``run.py calibrate``: fit the monotone map from the restored model's raw score to P(positive) on the
+        validation files (+ ``validation_weight_files``) -- an exact isotonic regression of ONE forward's scores
+        (ops/kernels.py ``isotonic_fit``) -- and write it as ``calibration.json`` into the checkpoint's directory
+        (it belongs to that step and is pruned with it) and, one line per block ``score_lo score_hi probability
+        weight positives``, as ``<log_dir>/calibration_blocks.txt`` (the reliability table).  Prints
+        ``calibrate: examples N blocks M loss L_before -> L_after ratio R_before -> 1.00000000 (in-sample)``:
+        the validation loss of that forward, the same loss of the fitted values (from the blocks; a block whose
+        value is 0 or 1 adds 0), and the predicted over the observed positive weight before the fit (after it,
+        it is 1 by construction).  Multi-rank runs deal the examples as the validation does; rank 0 writes."""
+        c = self.cfg
+        if c.loss_type != "logistic":
+            raise CalibrationError(f"calibrate: needs loss_type = logistic (raw scores that are logits of a "
+                                   f"probability); this config has loss_type = {c.loss_type}")
+        if not c.validation_data_files:
+            raise CalibrationError("calibrate: needs [Train] validation_files, the held-out labelled set to fit on")
+        if not self.restore():
+            raise FileNotFoundError(f"no checkpoint found in {c.log_dir}")
+        vb = self.load_validation()
+        self.print("========", "calibrate", "========")
+        fo = self.model.forward(vb, loss=c.loss_type)
+        loss = self._global_loss(float(fo.loss_sum), vb.B)
+        scores, labels, weights = gather_dealt(self.ctx if self.world > 1 else None,
+                                               [fo.pred[:vb.B].contiguous(), vb.labels, vb.weights])
+        fit = isotonic_fit(scores, labels, weights)
+        try:
+            blocks = fit.count()
+        except ValueError as e:  # (a NaN score: there is no fit)
+            raise CalibrationError(f"calibrate: {e}") from None
+        if blocks == 0:
+            raise CalibrationError("calibrate: the validation examples carry no weight")
+        lo, hi, bw, by, bv = (t.cpu().numpy() for t in fit.blocks())
+        total_w, pos_w = fit.totals()
+        n = scores.numel()
+        sig = torch.sigmoid(scores.to(torch.float64))
+        predicted = float((sig if weights is None else sig * weights.to(torch.float64)).sum())
+        ratio = predicted / pos_w if pos_w > 0 else float("nan")
+        # (the validation loss is the weighted loss sum over the number of examples: the same mean here)
+        after = log_loss_sum_of_blocks(bw, by, bv) / n
+        cal = Calibrator.from_fit(fit, examples=n, global_step=int(self.model.global_step),
+                                  loss_before=loss, loss_after=after, ratio_before=ratio)
+        res = {"examples": n, "blocks": blocks, "loss_before": loss, "loss_after": after, "ratio_before": ratio,
+               "calibrator": cal}
+        if self.rank == 0:
+            res["file"] = cal.save(os.path.join(self.restored_from, CALIBRATION_FILE))
+            res["blocks_file"] = os.path.join(c.log_dir, "calibration_blocks.txt")
+            with open(res["blocks_file"], "w") as f:
+                for b in range(blocks):
+                    f.write("%s %s %s %s %s\n" % (str(np.float32(lo[b])), str(np.float32(hi[b])),
+                                                  str(np.float32(bv[b])), bw[b], by[b]))
+        self.print("calibrate: examples %d blocks %d loss %.8f -> %.8f ratio %.8f -> 1.00000000 (in-sample)"
+                   % (n, blocks, loss, after, ratio))
+        return res
 
     # ------------------------------------------------------------------
     def evaluate(self) -> dict:
