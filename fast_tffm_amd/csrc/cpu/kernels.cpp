@@ -10,6 +10,7 @@
 
 #include "../hash64.h"
 #include "../iso_hull.h"
+#include "../score_key.h"
 #include "../topk_order.h"
 
 namespace fm {
@@ -287,6 +288,19 @@ void csr_rows(int B, const int* offsets, int* ex_of_occ) {
 }
 
 namespace {
+// (score key << 32) | example index of every score (score_key.h: bit patterns, no arithmetic on the score);
+// nans += the NaN scores.
+std::vector<uint64_t> keyed_scores(int n, const float* scores, uint64_t& nans) {
+  std::vector<uint64_t> kv(n > 0 ? n : 0);
+  for (int j = 0; j < n; ++j) {
+    uint32_t b;
+    std::memcpy(&b, scores + j, 4);
+    nans += score_is_nan(b);
+    kv[j] = (static_cast<uint64_t>(score_key(b)) << 32) | static_cast<uint32_t>(j);
+  }
+  return kv;
+}
+
 // One pass over the (key, index) order: a run of equal keys with positive weight rp and negative weight rn
 // after negatives of weight nlt adds rp * (nlt + (nlt + rn)).
 template <typename T>
@@ -316,16 +330,8 @@ void auc_pass(const std::vector<uint64_t>& kv, const float* labels, const float*
 }  // namespace
 
 void auc(int n, const float* scores, const float* labels, const float* weights, void* out) {
-  std::vector<uint64_t> kv(n > 0 ? n : 0);
   uint64_t nans = 0;
-  for (int j = 0; j < n; ++j) {
-    uint32_t b;
-    std::memcpy(&b, scores + j, 4);  // (bit patterns: no arithmetic on the score, denormals keep their order)
-    nans += (b & 0x7fffffffu) > 0x7f800000u;
-    if (b == 0x80000000u) b = 0u;    // -0.0 == +0.0
-    const uint32_t key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    kv[j] = (static_cast<uint64_t>(key) << 32) | static_cast<uint32_t>(j);
-  }
+  std::vector<uint64_t> kv = keyed_scores(n, scores, nans);
   std::sort(kv.begin(), kv.end());
   if (weights) auc_pass<double>(kv, labels, weights, nans, static_cast<double*>(out));
   else auc_pass<uint64_t>(kv, labels, weights, nans, static_cast<uint64_t*>(out));
@@ -385,17 +391,13 @@ void gauc_pass(const std::vector<std::pair<uint64_t, uint32_t>>& kv, long long G
 
 void gauc(int n, long long G, const float* scores, const float* labels, const float* weights, const int* groups,
           void* out, void* rec) {
-  std::vector<std::pair<uint64_t, uint32_t>> kv(n > 0 ? n : 0);
   uint64_t nans = 0;
+  const std::vector<uint64_t> ks = keyed_scores(n, scores, nans);
+  std::vector<std::pair<uint64_t, uint32_t>> kv(ks.size());
   for (int j = 0; j < n; ++j) {
-    uint32_t b;
-    std::memcpy(&b, scores + j, 4);
-    nans += (b & 0x7fffffffu) > 0x7f800000u;
-    if (b == 0x80000000u) b = 0u;
-    const uint32_t key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
     const uint32_t g = static_cast<uint32_t>(groups[j]) < static_cast<uint64_t>(G) ? static_cast<uint32_t>(groups[j])
                                                                                   : static_cast<uint32_t>(G - 1);
-    kv[j] = {(static_cast<uint64_t>(g) << 32) | key, static_cast<uint32_t>(j)};
+    kv[j] = {(static_cast<uint64_t>(g) << 32) | (ks[j] >> 32), static_cast<uint32_t>(j)};
   }
   std::sort(kv.begin(), kv.end());
   if (weights) gauc_pass<double>(kv, G, labels, weights, nans, out, static_cast<double*>(rec));
@@ -462,8 +464,8 @@ void isotonic_pass(const std::vector<uint64_t>& kv, const float* labels, const f
   const int m = c - 1;  // (H[0] = 0, H[m] = n)
   for (int b = 0; b < m; ++b) {
     const int p = H[b], q = H[b + 1];
-    const uint32_t bl = iso::key_to_bits(static_cast<uint32_t>(kv[p] >> 32));
-    const uint32_t bh = iso::key_to_bits(static_cast<uint32_t>(kv[q - 1] >> 32));
+    const uint32_t bl = score_key_bits(static_cast<uint32_t>(kv[p] >> 32));
+    const uint32_t bh = score_key_bits(static_cast<uint32_t>(kv[q - 1] >> 32));
     std::memcpy(lo + b, &bl, 4);
     std::memcpy(hi + b, &bh, 4);
     W[b] = cW[q] - cW[p];
@@ -482,16 +484,8 @@ void isotonic_pass(const std::vector<uint64_t>& kv, const float* labels, const f
 
 void isotonic(int n, const float* scores, const float* labels, const float* weights, float* lo, float* hi, void* W,
               void* Y, double* v, double* fitted, void* out, int tile) {
-  std::vector<uint64_t> kv(n > 0 ? n : 0);
   uint64_t nans = 0;
-  for (int j = 0; j < n; ++j) {
-    uint32_t b;
-    std::memcpy(&b, scores + j, 4);
-    nans += (b & 0x7fffffffu) > 0x7f800000u;
-    if (b == 0x80000000u) b = 0u;
-    const uint32_t key = (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-    kv[j] = (static_cast<uint64_t>(key) << 32) | static_cast<uint32_t>(j);
-  }
+  std::vector<uint64_t> kv = keyed_scores(n, scores, nans);
   std::sort(kv.begin(), kv.end());
   if (weights)
     isotonic_pass<double>(kv, labels, weights, nans, lo, hi, static_cast<double*>(W), static_cast<double*>(Y), v,

@@ -21,7 +21,7 @@
 //   scan:  one block turns the tile counts into exclusive 64-bit offsets, in tile order; the last
 //          entry is the total (the one value the host reads, to size the output).
 //   emit:  one block per tile writes the set bits' row numbers at the tile's offset, in row order.
-// (Included by module.hip after auc.hip and init.hip: auc_block_scan and the init functions.)
+// (Included by module.hip after metric_common.hip and init.hip: auc_block_scan and the init functions.)
 #include "fm_common.h"
 
 namespace fm {

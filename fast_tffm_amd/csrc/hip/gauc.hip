@@ -7,14 +7,13 @@
 //   valid iff P_g > 0 and N_g > 0;  AUC_g = U2_g / (2 P_g N_g),  W_g = P_g + N_g
 //   GAUC = sum_valid W_g AUC_g / sum_valid W_g
 //
-// Scores are keyed, ordered and NaN-counted exactly as in auc.hip.  Two modes as there: unweighted in uint64
+// Scores are keyed, ordered and NaN-counted by metric_common.hip's score sort.  Two modes: unweighted in uint64
 // (the per-group records are exact integers), weighted in fp64; every sum has a fixed order and adds only
 // non-negative terms of ONE group (no group sum is a difference of two global prefixes), so the results are
 // bitwise the same run to run and a small group next to a huge one keeps its full precision.
 //
 // Launch chain (kernel boundaries order the steps; no host sync, the workspace is the caller's: capturable):
-//   key:     auc_key_kernel: key + example index per score, NaN count;
-//   sort 1:  launch_radix_sort over the 32 key bits, payload = example index;
+//   key, sort 1: launch_score_sort: key + example index per score, NaN count, stable sort by the 32 key bits;
 //   gather:  group id of every score-sorted position (the first sort's error word is saved here: the second
 //            sort reuses its workspace);
 //   sort 2:  the same stable sort over bits_for(G) bits of the group id -> (group, score) order;
@@ -36,7 +35,8 @@
 //             sort error word]; a nonzero sort error also sets the sticky device error word.
 // Groups of a few examples sit several to a wave (eight positions per lane, the segmented scan keeps them
 // apart); the same scan carries one group over any number of tiles.  Empty groups keep the zeros of the
-// chain's memset.  (Included by module.hip after auc.hip.)
+// chain's memset.  (Included by module.hip after metric_common.hip: the tile constants, auc_block_scan, auc_bound,
+// signed_weight, the workspace cursor and the argument check are defined there.)
 #include "fm_common.h"
 
 namespace fm {
@@ -130,6 +130,14 @@ __device__ inline void gauc_groups(const GaucArgs<T>& a, int j0, int (&g)[kAucIt
   gnext = j0 + kAucItems < a.n ? gauc_gid(a.sg[j0 + kAucItems], a.G) : -1;
 }
 
+// position j = j0 + q (< n) is the first / the last of its group (gprev == -1 at j == 0)
+__device__ inline bool gauc_head(const int (&g)[kAucItems], int q, int gprev) {
+  return g[q] != (q ? g[q - 1] : gprev);
+}
+__device__ inline bool gauc_tail(const int (&g)[kAucItems], int q, int gnext, int j, int n) {
+  return j == n - 1 || g[q] != (q + 1 < kAucItems ? g[q + 1] : gnext);
+}
+
 __global__ __launch_bounds__(kBlock) void gauc_gather_kernel(int n, int G, const int* groups, const int* sidx,
                                                              uint32_t* gk, const int* sort_err, int* err_out) {
   if (blockIdx.x == 0 && threadIdx.x == 0) *err_out = *sort_err;
@@ -153,22 +161,16 @@ __global__ __launch_bounds__(kBlock) void gauc_tile_kernel(GaucArgs<T> a) {
   for (int q = 0; q < kAucItems; ++q) {
     const int j = j0 + q;
     if (j >= a.n) continue;
-    if (g[q] != (q ? g[q - 1] : gprev)) {  // head (gprev == -1 at j == 0)
+    if (gauc_head(g, q, gprev)) {
       a.grange[2 * (size_t)g[q]] = j;
       neg = 0;
       pos = 0;
       hf = true;
     }
-    if (j == a.n - 1 || g[q] != (q + 1 < kAucItems ? g[q + 1] : gnext)) a.grange[2 * (size_t)g[q] + 1] = j + 1;
-    float s = 0.f;
-    uint32_t key = 0u;
-    if ((unsigned)ex[q] < (unsigned)a.n) {  // (always, unless a sort failed: its error word is reported)
-      const float w = a.weights ? a.weights[ex[q]] : 1.f;
-      s = a.labels[ex[q]] > 0.f ? w : -w;
-      key = a.keys[ex[q]];
-    }
+    if (gauc_tail(g, q, gnext, j, a.n)) a.grange[2 * (size_t)g[q] + 1] = j + 1;
+    const float s = signed_weight(a.labels, a.weights, ex[q], a.n);
     a.sv[j] = __float_as_uint(s);
-    a.fkeys[j] = key;
+    a.fkeys[j] = (unsigned)ex[q] < (unsigned)a.n ? a.keys[ex[q]] : 0u;  // (as signed_weight: a failed sort)
     if (s > 0.f) pos += (T)s;
     else neg += (T)(-s);
   }
@@ -221,7 +223,7 @@ __global__ __launch_bounds__(kBlock) void gauc_nex_kernel(GaucArgs<T> a) {
     const float s = __uint_as_float(sv[q]);
     m[q] = (j < a.n && !(s > 0.f)) ? (T)(-s) : (T)0;
     p[q] = (j < a.n && s > 0.f) ? (T)s : (T)0;
-    if (j < a.n && g[q] != (q ? g[q - 1] : gprev)) {
+    if (j < a.n && gauc_head(g, q, gprev)) {
       neg = 0;
       pos = 0;
       hf = true;
@@ -239,14 +241,14 @@ __global__ __launch_bounds__(kBlock) void gauc_nex_kernel(GaucArgs<T> a) {
   for (int q = 0; q < kAucItems; ++q) {
     const int j = j0 + q;
     if (j >= a.n) continue;
-    if (g[q] != (q ? g[q - 1] : gprev)) {
+    if (gauc_head(g, q, gprev)) {
       run_n = 0;
       run_p = 0;
     }
     a.ex[j] = run_n;
     run_n += m[q];
     run_p += p[q];
-    if (j == a.n - 1 || g[q] != (q + 1 < kAucItems ? g[q + 1] : gnext)) {
+    if (gauc_tail(g, q, gnext, j, a.n)) {
       a.rec[3 * (size_t)g[q] + 1] = run_p;
       a.rec[3 * (size_t)g[q] + 2] = run_n;
     }
@@ -274,7 +276,7 @@ __global__ __launch_bounds__(kBlock) void gauc_rank_kernel(GaucArgs<T> a) {
     const int j = j0 + q;
     u[q] = 0;
     if (j >= a.n) continue;
-    const bool head = g[q] != (q ? g[q - 1] : gprev);
+    const bool head = gauc_head(g, q, gprev);
     if (head) {
       usum = 0;
       hf = true;
@@ -286,7 +288,7 @@ __global__ __launch_bounds__(kBlock) void gauc_rank_kernel(GaucArgs<T> a) {
       continue;
     }
     if (!(have && tie_prev)) {
-      const bool tail = j == a.n - 1 || g[q] != (q + 1 < kAucItems ? g[q + 1] : gnext);
+      const bool tail = gauc_tail(g, q, gnext, j, a.n);
       const bool tie_next = !tail && (q + 1 < kAucItems ? k[q + 1] : knext) == k[q];
       lb = j;
       ub = j + 1;
@@ -310,12 +312,12 @@ __global__ __launch_bounds__(kBlock) void gauc_rank_kernel(GaucArgs<T> a) {
   for (int q = 0; q < kAucItems; ++q) {
     const int j = j0 + q;
     if (j >= a.n) continue;
-    if (g[q] != (q ? g[q - 1] : gprev)) {
+    if (gauc_head(g, q, gprev)) {
       run = 0;
       seen = true;
     }
     run += u[q];
-    if (j == a.n - 1 || g[q] != (q + 1 < kAucItems ? g[q + 1] : gnext)) {
+    if (gauc_tail(g, q, gnext, j, a.n)) {
       if (seen) a.rec[3 * (size_t)g[q]] = run;
       else a.fu[blockIdx.x] = run;
     }
@@ -346,11 +348,30 @@ __global__ __launch_bounds__(kAucBaseThreads) void gauc_ubase_kernel(GaucArgs<T>
   }
 }
 
+// The block's sums (in thread order) of a thread's four quantities, packed by thread 0 into the 32-byte record o:
+// [sum W AUC (fp64), sum W (T), valid groups, examples in valid groups].
 template <typename T>
-__global__ __launch_bounds__(kBlock) void gauc_group_kernel(GaucArgs<T> a) {
+__device__ inline void gauc_pack_sums(double wa, T w, uint64_t valid, uint64_t exs, unsigned char* o) {
   __shared__ double shd[kWavesPerBlock];
   __shared__ T sht[kWavesPerBlock];
   __shared__ uint64_t shu[kWavesPerBlock];
+  double ed, td;
+  T et, tt;
+  uint64_t eu, tv, te;
+  auc_block_scan<double, kWavesPerBlock>(wa, ed, td, shd);
+  auc_block_scan<T, kWavesPerBlock>(w, et, tt, sht);
+  auc_block_scan<uint64_t, kWavesPerBlock>(valid, eu, tv, shu);
+  auc_block_scan<uint64_t, kWavesPerBlock>(exs, eu, te, shu);
+  if (threadIdx.x == 0) {
+    *reinterpret_cast<double*>(o) = td;
+    *reinterpret_cast<T*>(o + 8) = tt;
+    *reinterpret_cast<uint64_t*>(o + 16) = tv;
+    *reinterpret_cast<uint64_t*>(o + 24) = te;
+  }
+}
+
+template <typename T>
+__global__ __launch_bounds__(kBlock) void gauc_group_kernel(GaucArgs<T> a) {
   const long long g = (long long)blockIdx.x * kBlock + threadIdx.x;
   double wa = 0.0;
   T w = 0;
@@ -364,27 +385,11 @@ __global__ __launch_bounds__(kBlock) void gauc_group_kernel(GaucArgs<T> a) {
       exs = (uint64_t)(a.grange[2 * (size_t)g + 1] - a.grange[2 * (size_t)g]);
     }
   }
-  double ed, td;
-  T et, tt;
-  uint64_t eu, tv, te;
-  auc_block_scan<double, kWavesPerBlock>(wa, ed, td, shd);
-  auc_block_scan<T, kWavesPerBlock>(w, et, tt, sht);
-  auc_block_scan<uint64_t, kWavesPerBlock>(valid, eu, tv, shu);
-  auc_block_scan<uint64_t, kWavesPerBlock>(exs, eu, te, shu);
-  if (threadIdx.x == 0) {
-    unsigned char* o = a.gpart + 32 * (size_t)blockIdx.x;
-    *reinterpret_cast<double*>(o) = td;
-    *reinterpret_cast<T*>(o + 8) = tt;
-    *reinterpret_cast<uint64_t*>(o + 16) = tv;
-    *reinterpret_cast<uint64_t*>(o + 24) = te;
-  }
+  gauc_pack_sums<T>(wa, w, valid, exs, a.gpart + 32 * (size_t)blockIdx.x);
 }
 
 template <typename T>
 __global__ __launch_bounds__(kBlock) void gauc_final_kernel(GaucArgs<T> a) {
-  __shared__ double shd[kWavesPerBlock];
-  __shared__ T sht[kWavesPerBlock];
-  __shared__ uint64_t shu[kWavesPerBlock];
   // thread t sums its contiguous share of the blocks' partials in block order, then the block in thread order
   const int per = (a.gblocks + kBlock - 1) / kBlock;
   double wa = 0.0;
@@ -398,20 +403,10 @@ __global__ __launch_bounds__(kBlock) void gauc_final_kernel(GaucArgs<T> a) {
     valid += *reinterpret_cast<const uint64_t*>(o + 16);
     exs += *reinterpret_cast<const uint64_t*>(o + 24);
   }
-  double ed, td;
-  T et, tt;
-  uint64_t eu, tv, te;
-  auc_block_scan<double, kWavesPerBlock>(wa, ed, td, shd);
-  auc_block_scan<T, kWavesPerBlock>(w, et, tt, sht);
-  auc_block_scan<uint64_t, kWavesPerBlock>(valid, eu, tv, shu);
-  auc_block_scan<uint64_t, kWavesPerBlock>(exs, eu, te, shu);
+  unsigned char* o = static_cast<unsigned char*>(a.out);
+  gauc_pack_sums<T>(wa, w, valid, exs, o);
   if (threadIdx.x == 0) {
     const int err = *a.sort_err1 | *a.sort_err2;
-    unsigned char* o = static_cast<unsigned char*>(a.out);
-    *reinterpret_cast<double*>(o) = td;
-    *reinterpret_cast<T*>(o + 8) = tt;
-    *reinterpret_cast<uint64_t*>(o + 16) = tv;
-    *reinterpret_cast<uint64_t*>(o + 24) = te;
     *reinterpret_cast<uint64_t*>(o + 32) = (uint64_t)*a.nan_count;
     *reinterpret_cast<uint64_t*>(o + 40) = (uint64_t)(unsigned)err;
     if (err) atomicOr(&g_fm_dev_error, kDevErrSort);
@@ -427,30 +422,25 @@ struct GaucLayout {
 };
 
 static GaucLayout gauc_layout(int n, long long G) {
+  WsCursor c;
   GaucLayout l{};
   l.ntiles = (n + kAucTile - 1) / kAucTile;
   l.gblocks = (int)((G + kBlock - 1) / kBlock);
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += rs_align(bytes);
-    return o;
-  };
-  l.keys = take(4 * (size_t)n);
-  l.bufa = take(4 * (size_t)n);
-  l.bufb = take(4 * (size_t)n);
-  l.si1 = take(4 * (size_t)n);
-  l.gk = take(4 * (size_t)n);
-  l.sg = take(4 * (size_t)n);
-  l.si2 = take(4 * (size_t)n);
-  l.ex = take(8 * (size_t)n);
-  l.tiles = take(8 * 6 * (size_t)l.ntiles);
-  l.tflag = take(4 * (size_t)l.ntiles);
-  l.grange = take(8 * (size_t)G);
-  l.gpart = take(32 * (size_t)l.gblocks);
-  l.misc = take(32);
-  l.sort = take(radix_sort_ws_bytes(n));
-  l.total = off;
+  l.keys = c.take(4 * (size_t)n);
+  l.bufa = c.take(4 * (size_t)n);
+  l.bufb = c.take(4 * (size_t)n);
+  l.si1 = c.take(4 * (size_t)n);
+  l.gk = c.take(4 * (size_t)n);
+  l.sg = c.take(4 * (size_t)n);
+  l.si2 = c.take(4 * (size_t)n);
+  l.ex = c.take(8 * (size_t)n);
+  l.tiles = c.take(8 * 6 * (size_t)l.ntiles);
+  l.tflag = c.take(4 * (size_t)l.ntiles);
+  l.grange = c.take(8 * (size_t)G);
+  l.gpart = c.take(32 * (size_t)l.gblocks);
+  l.misc = c.take(32);
+  l.sort = c.take(radix_sort_ws_bytes(n));
+  l.total = c.off;
   return l;
 }
 
@@ -483,21 +473,17 @@ static int launch_gauc_t(const float* scores, const float* labels, const float* 
   T* tiles = reinterpret_cast<T*>(ws + l.tiles);
   int* grange = reinterpret_cast<int*>(ws + l.grange);
   unsigned* nan_count = reinterpret_cast<unsigned*>(ws + l.misc);
-  int* err1 = reinterpret_cast<int*>(ws + l.misc) + 1;
+  int* err1 = reinterpret_cast<int*>(ws + l.misc) + 1;  // (written by the gather kernel)
   void* sort_ws = ws + l.sort;
-  const size_t sort_bytes = radix_sort_ws_bytes(n);
-  hipError_t e = hipMemsetAsync(nan_count, 0, 8, st);
-  if (e == hipSuccess) e = hipMemsetAsync(grange, 0, 8 * (size_t)G, st);
+  hipError_t e = hipMemsetAsync(grange, 0, 8 * (size_t)G, st);
   if (e == hipSuccess) e = hipMemsetAsync(rec, 0, 24 * (size_t)G, st);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(auc_key_kernel, dim3(fill_grid(n, kBlock, 2048)), dim3(kBlock), 0, st, n,
-                     reinterpret_cast<const uint32_t*>(scores), keys, idx, nan_count);
-  int se = launch_radix_sort(keys, idx, sk1, si1, n, 32, sort_ws, sort_bytes, st);
+  ScoreSort s1;
+  int se = launch_score_sort(scores, n, keys, idx, sk1, si1, nan_count, sort_ws, st, s1);
   if (se != 0) return se;
-  const int* sort_err = radix_sort_error(sort_ws, n);
   hipLaunchKernelGGL(gauc_gather_kernel, dim3(fill_grid(n, kBlock, 2048)), dim3(kBlock), 0, st, n, G, groups, si1, gk,
-                     sort_err, err1);
-  se = launch_radix_sort(gk, si1, sg, si2, n, gauc_bits_for(G), sort_ws, sort_bytes, st);
+                     s1.sort_err, err1);
+  se = launch_radix_sort(gk, si1, sg, si2, n, gauc_bits_for(G), sort_ws, radix_sort_ws_bytes(n), st);
   if (se != 0) return se;
   const size_t nt = (size_t)l.ntiles;
   GaucArgs<T> a{n, l.ntiles, G, l.gblocks, labels, weights, keys, reinterpret_cast<const int*>(sg), si2,
@@ -505,7 +491,7 @@ static int launch_gauc_t(const float* scores, const float* labels, const float* 
                 reinterpret_cast<uint32_t*>(idx) /* so is the identity index: the signed weights */,
                 reinterpret_cast<T*>(ws + l.ex), grange, reinterpret_cast<int*>(ws + l.tflag), tiles, tiles + nt,
                 tiles + 2 * nt, tiles + 3 * nt, tiles + 4 * nt, tiles + 5 * nt, static_cast<T*>(rec),
-                reinterpret_cast<unsigned char*>(ws + l.gpart), nan_count, err1, sort_err, out};
+                reinterpret_cast<unsigned char*>(ws + l.gpart), nan_count, err1, s1.sort_err, out};
   hipLaunchKernelGGL(gauc_tile_kernel<T>, dim3(l.ntiles), dim3(kBlock), 0, st, a);
   hipLaunchKernelGGL(gauc_base_kernel<T>, dim3(1), dim3(kAucBaseThreads), 0, st, a);
   hipLaunchKernelGGL(gauc_nex_kernel<T>, dim3(l.ntiles), dim3(kBlock), 0, st, a);
@@ -521,11 +507,8 @@ static int launch_gauc_t(const float* scores, const float* labels, const float* 
 // st.  0 or a hip error code; -1: bad arguments; -2: workspace too small; -5: n >= 2^30; -6: G outside [1, 2^31).
 int launch_gauc(const float* scores, const float* labels, const float* weights, const int* groups, int n,
                 long long G, void* out, void* rec, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (n < 1 || !scores || !labels || !groups || !out || !rec || !ws) return -1;
-  if ((reinterpret_cast<uintptr_t>(ws) & 15) || (reinterpret_cast<uintptr_t>(out) & 7) ||
-      (reinterpret_cast<uintptr_t>(rec) & 7))
-    return -1;  // (16-byte loads)
-  if ((unsigned)n > kOsCnt) return -5;
+  if (!groups || !rec || (reinterpret_cast<uintptr_t>(rec) & 7)) return -1;
+  if (const int rc = metric_check_args(n, scores, labels, out, ws)) return rc;
   if (G < 1 || G >= (1ll << 31)) return -6;
   const GaucLayout l = gauc_layout(n, G);
   if (ws_bytes < l.total) return -2;

@@ -2,19 +2,17 @@
 // P(positive), for recalibrating a trained model on held-out data (ops/kernels.py isotonic_fit; the reference has
 // no calibration).
 //
-// With the examples sorted by score (auc.hip's order: IEEE fp32 values, -0.0 == +0.0, NaN scores counted), cW[j] /
-// cY[j] the weight / positive weight of the sorted positions < j, and position j a candidate iff j == 0, j == n or
+// With the examples sorted by score (score_key.h's order: IEEE fp32 values, -0.0 == +0.0, NaN scores counted), cW[j]
+// / cY[j] the weight / positive weight of the sorted positions < j, and position j a candidate iff j == 0, j == n or
 // the keys at j - 1 and j differ (tied scores share one value), the fit is the slope of the lower convex hull of
 // the candidate points (cW[j], cY[j]) with the minimal vertex set (iso_hull.h: collinear points are no vertices).
 // Consecutive vertices H[b], H[b + 1] are block b: sorted positions [H[b], H[b + 1]), value Y_b / W_b in fp64.
-// Two modes as in auc.hip: unweighted in uint64 (exact), weighted (w > 0) in fp64 in a fixed order; both bitwise
-// reproducible run to run.
+// Two modes: unweighted in uint64 (exact), weighted (w > 0) in fp64 in a fixed order; both bitwise reproducible run
+// to run.
 //
 // Launch chain (no kernel waits for another workgroup; kernel boundaries order the steps; no host read):
-//   key, sort: as auc.hip;
-//   tile:    signed weight of every sorted position (the only gather through the sorted index), tile totals;
-//   base:    one block scans the tile totals;
-//   cum:     cW[0 .. n], cY[0 .. n];
+//   key, sort, tile, base, cum: metric_common.hip's score sort and prefix chain with the channels (all,
+//            positives): cW = cum[0], cY = cum[1], each [0 .. n]; tot = [W, Y];
 //   leaf:    one workgroup per tile of 2048 points of [0, n]: the tile's points staged in LDS, the serial stack per
 //            thread over its 8 points, 8 bridge merges in LDS, the vertex positions to hullA[tile start ...] and
 //            their count (a hull never has more vertices than points: every node's list fits in the node's own
@@ -25,29 +23,15 @@
 //   extract: block arrays lo, hi (fp32 scores of the block's first / last position), W, Y, v = Y / W and the
 //            record [blocks, total weight, positive weight, nan count, sort error word];
 //   fitted:  (optional) v of its block for every example, in input order.
-// (Included by module.hip after auc.hip: auc_key_kernel, auc_block_scan, load8 and the radix sort come from there.)
+// (Included by module.hip after metric_common.hip.)
 #include "../iso_hull.h"
 #include "fm_common.h"
 
 namespace fm {
 
 template <typename T>
-struct IsoArgs {
-  int n, ntiles, npt, ntl;  // npt = n + 1 points, ntl = their tiles
-  const float* labels;
-  const float* weights;    // null: all ones
-  const uint32_t* skeys;   // [n] sorted keys
-  const int* sidx;         // [n] example index of every sorted position
-  uint32_t* sv;            // [n] float bits: +w (positive) / -w (negative) of every sorted position
-  T* cW;                   // [n + 1]
-  T* cY;                   // [n + 1]
-  T* tile_w;               // [ntiles] weight of the tile
-  T* tile_y;               // [ntiles] positive weight of the tile
-  T* base_w;               // [ntiles] weight before the tile
-  T* base_y;               // [ntiles]
-  T* tot;                  // [2] W, Y
-  const unsigned* nan_count;
-  const int* sort_err;
+struct IsoArgs : PrefixArgs<T> {
+  int npt, ntl;            // npt = n + 1 points, ntl = their tiles
   float* blo;              // block arrays, [n] each
   float* bhi;
   T* bW;
@@ -56,89 +40,6 @@ struct IsoArgs {
   double* fitted;          // [n] or null
   T* out;                  // [5] blocks, W, Y, nan count, sort error word
 };
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void iso_tile_kernel(IsoArgs<T> a) {
-  __shared__ T sh[kWavesPerBlock];
-  const int j0 = blockIdx.x * kAucTile + threadIdx.x * kAucItems;
-  int ex[kAucItems];
-  load8(a.sidx, j0, a.n, ex, -1);
-  T all = 0, pos = 0;
-#pragma unroll
-  for (int q = 0; q < kAucItems; ++q) {
-    if (j0 + q >= a.n) continue;
-    float s = 0.f;
-    if ((unsigned)ex[q] < (unsigned)a.n) {  // (always, unless the sort failed: its error word is reported)
-      const float w = a.weights ? a.weights[ex[q]] : 1.f;
-      s = a.labels[ex[q]] > 0.f ? w : -w;
-    }
-    a.sv[j0 + q] = __float_as_uint(s);
-    if (s > 0.f) pos += (T)s, all += (T)s;
-    else all += (T)(-s);
-  }
-  T e, t;
-  auc_block_scan<T, kWavesPerBlock>(all, e, t, sh);
-  if (threadIdx.x == 0) a.tile_w[blockIdx.x] = t;
-  auc_block_scan<T, kWavesPerBlock>(pos, e, t, sh);
-  if (threadIdx.x == 0) a.tile_y[blockIdx.x] = t;
-}
-
-template <typename T>
-__global__ __launch_bounds__(kAucBaseThreads) void iso_base_kernel(IsoArgs<T> a) {
-  constexpr int NW = kAucBaseThreads / kWave;
-  __shared__ T sh[NW];
-  T cw = 0, cy = 0;
-  for (int c = 0; c < a.ntiles; c += kAucBaseThreads) {
-    const int t = c + threadIdx.x;
-    const bool ok = t < a.ntiles;
-    T e, tw, ty;
-    auc_block_scan<T, NW>(ok ? a.tile_w[t] : (T)0, e, tw, sh);
-    if (ok) a.base_w[t] = cw + e;
-    cw += tw;
-    auc_block_scan<T, NW>(ok ? a.tile_y[t] : (T)0, e, ty, sh);
-    if (ok) a.base_y[t] = cy + e;
-    cy += ty;
-  }
-  if (threadIdx.x == 0) {
-    a.tot[0] = cw;
-    a.tot[1] = cy;
-  }
-}
-
-template <typename T>
-__global__ __launch_bounds__(kBlock) void iso_cum_kernel(IsoArgs<T> a) {
-  __shared__ T sh[kWavesPerBlock];
-  const int j0 = blockIdx.x * kAucTile + threadIdx.x * kAucItems;
-  uint32_t sv[kAucItems];
-  load8(a.sv, j0, a.n, sv, 0u);
-  T mw[kAucItems], my[kAucItems], all = 0, pos = 0;
-#pragma unroll
-  for (int q = 0; q < kAucItems; ++q) {
-    const float s = __uint_as_float(sv[q]);
-    const bool in = j0 + q < a.n;
-    my[q] = (in && s > 0.f) ? (T)s : (T)0;
-    mw[q] = in ? (s > 0.f ? (T)s : (T)(-s)) : (T)0;
-    all += mw[q];
-    pos += my[q];
-  }
-  T ew, ey, t;
-  auc_block_scan<T, kWavesPerBlock>(all, ew, t, sh);
-  auc_block_scan<T, kWavesPerBlock>(pos, ey, t, sh);
-  T rw = a.base_w[blockIdx.x] + ew, ry = a.base_y[blockIdx.x] + ey;
-#pragma unroll
-  for (int q = 0; q < kAucItems; ++q) {
-    const int j = j0 + q;
-    if (j >= a.n) continue;
-    a.cW[j] = rw;
-    a.cY[j] = ry;
-    rw += mw[q];
-    ry += my[q];
-    if (j == a.n - 1) {
-      a.cW[a.n] = rw;
-      a.cY[a.n] = ry;
-    }
-  }
-}
 
 // Points of tile t: [t * kAucTile, min((t + 1) * kAucTile, npt)), staged in LDS.  Every thread builds the hull of
 // its 8 consecutive points with the serial stack; 8 levels then merge sibling hulls by their bridges (one thread
@@ -155,8 +56,8 @@ __global__ __launch_bounds__(kBlock) void iso_leaf_kernel(IsoArgs<T> a, int* hul
   const int c = min(kAucTile, a.npt - base);
   for (int k = tid; k < c; k += kBlock) {
     const int j = base + k;
-    w[k] = a.cW[j];
-    y[k] = a.cY[j];
+    w[k] = a.cum[0][j];
+    y[k] = a.cum[1][j];
     cand[k] = j == 0 || j == a.n || a.skeys[j - 1] != a.skeys[j];
   }
   __syncthreads();
@@ -220,7 +121,7 @@ __global__ __launch_bounds__(kBlock) void iso_merge_kernel(IsoArgs<T> a, int lev
     nR = min(max(scnt[tr], 0), (int)min(span, (long long)a.npt - pr));
     R = src + pr;
     if (nL > 0 && nR > 0) {  // (every thread the same search: the loads broadcast)
-      const iso::Diagram<T> d{a.cW, a.cY, a.n};
+      const iso::Diagram<T> d{a.cum[0], a.cum[1], a.n};
       iso::bridge<T>(d, L, nL, R, nR, a_, b_);
       a_ = min(max(a_, 0), nL - 1);
       b_ = min(max(b_, 0), nR - 1);
@@ -238,9 +139,9 @@ __global__ __launch_bounds__(kBlock) void iso_extract_kernel(IsoArgs<T> a, const
   const int m = c > 1 ? c - 1 : 0;
   for (int b = blockIdx.x * kBlock + threadIdx.x; b < m; b += gridDim.x * kBlock) {
     const int p = min(max(H[b], 0), a.n - 1), q = min(max(H[b + 1], 1), a.n);
-    a.blo[b] = __uint_as_float(iso::key_to_bits(a.skeys[p]));
-    a.bhi[b] = __uint_as_float(iso::key_to_bits(a.skeys[q - 1]));
-    const T W = a.cW[q] - a.cW[p], Y = a.cY[q] - a.cY[p];
+    a.blo[b] = __uint_as_float(score_key_bits(a.skeys[p]));
+    a.bhi[b] = __uint_as_float(score_key_bits(a.skeys[q - 1]));
+    const T W = a.cum[0][q] - a.cum[0][p], Y = a.cum[1][q] - a.cum[1][p];
     a.bW[b] = W;
     a.bY[b] = Y;
     a.bv[b] = (double)Y / (double)W;
@@ -267,42 +168,29 @@ __global__ __launch_bounds__(kBlock) void iso_fitted_kernel(IsoArgs<T> a, const 
   }
 }
 
-// Workspace: [keys n | block lo][idx n | block hi][sorted keys n][sorted idx n][sv n][cW n + 1][cY n + 1]
-// [tile_w, tile_y, base_w, base_y: ntiles each][tot 2 + nan count][hullA, hullB: ntl * 2048 each][cntA, cntB: ntl
-// each][block W, Y, v: n each][sort workspace]  (keys / idx are dead after the sort: the block scores reuse them)
+// Workspace: the prefix chain's pieces (two prefixes: cW, cY), then [hullA, hullB: ntl * 2048 each][cntA, cntB:
+// ntl each][block W, Y, v: n each][sort workspace].  The chain's keys / idx pieces are dead after the sort: the
+// block scores lo / hi reuse them.
 struct IsoLayout {
-  size_t keys, idx, skeys, sidx, sv, cw, cy, tiles, misc, hull_a, hull_b, cnt_a, cnt_b, bw, by, bv, sort, total;
-  int ntiles, ntl;
+  PrefixLayout p;
+  size_t hull_a, hull_b, cnt_a, cnt_b, bw, by, bv, sort, total;
+  int ntl;
 };
 
 static IsoLayout iso_layout(int n) {
+  WsCursor c;
   IsoLayout l{};
-  l.ntiles = (n + kAucTile - 1) / kAucTile;
   l.ntl = n / kAucTile + 1;  // ceil((n + 1) / tile)
-  size_t off = 0;
-  auto take = [&](size_t bytes) {
-    const size_t o = off;
-    off += rs_align(bytes);
-    return o;
-  };
-  l.keys = take(4 * (size_t)n);
-  l.idx = take(4 * (size_t)n);
-  l.skeys = take(4 * (size_t)n);
-  l.sidx = take(4 * (size_t)n);
-  l.sv = take(4 * (size_t)n);
-  l.cw = take(8 * ((size_t)n + 1));
-  l.cy = take(8 * ((size_t)n + 1));
-  l.tiles = take(8 * 4 * (size_t)l.ntiles);
-  l.misc = take(32);
-  l.hull_a = take(4 * (size_t)l.ntl * kAucTile);
-  l.hull_b = take(4 * (size_t)l.ntl * kAucTile);
-  l.cnt_a = take(4 * (size_t)l.ntl);
-  l.cnt_b = take(4 * (size_t)l.ntl);
-  l.bw = take(8 * (size_t)n);
-  l.by = take(8 * (size_t)n);
-  l.bv = take(8 * (size_t)n);
-  l.sort = take(radix_sort_ws_bytes(n));
-  l.total = off;
+  l.p = prefix_layout(c, n, IsoChannels::kSecondPrefix);
+  l.hull_a = c.take(4 * (size_t)l.ntl * kAucTile);
+  l.hull_b = c.take(4 * (size_t)l.ntl * kAucTile);
+  l.cnt_a = c.take(4 * (size_t)l.ntl);
+  l.cnt_b = c.take(4 * (size_t)l.ntl);
+  l.bw = c.take(8 * (size_t)n);
+  l.by = c.take(8 * (size_t)n);
+  l.bv = c.take(8 * (size_t)n);
+  l.sort = c.take(radix_sort_ws_bytes(n));
+  l.total = c.off;
   return l;
 }
 
@@ -316,41 +204,20 @@ size_t isotonic_workspace_bytes(long long n) {
 // Byte offsets of the block arrays lo, hi (fp32), W, Y (uint64 / fp64), v (fp64) in the workspace, n >= 1.
 void isotonic_block_offsets(int n, size_t off[5]) {
   const IsoLayout l = iso_layout(n);
-  off[0] = l.keys, off[1] = l.idx, off[2] = l.bw, off[3] = l.by, off[4] = l.bv;
+  off[0] = l.p.keys, off[1] = l.p.idx, off[2] = l.bw, off[3] = l.by, off[4] = l.bv;
 }
 
 template <typename T>
 static int launch_isotonic_t(const float* scores, const float* labels, const float* weights, int n, double* fitted,
                              void* out, char* ws, const IsoLayout& l, hipStream_t st) {
-  uint32_t* keys = reinterpret_cast<uint32_t*>(ws + l.keys);
-  int* idx = reinterpret_cast<int*>(ws + l.idx);
-  uint32_t* skeys = reinterpret_cast<uint32_t*>(ws + l.skeys);
-  int* sidx = reinterpret_cast<int*>(ws + l.sidx);
-  T* tiles = reinterpret_cast<T*>(ws + l.tiles);
-  T* misc = reinterpret_cast<T*>(ws + l.misc);
-  unsigned* nan_count = reinterpret_cast<unsigned*>(misc + 2);
-  void* sort_ws = ws + l.sort;
-  hipError_t e = hipMemsetAsync(nan_count, 0, sizeof(unsigned), st);
-  if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(auc_key_kernel, dim3(fill_grid(n, kBlock, 2048)), dim3(kBlock), 0, st, n,
-                     reinterpret_cast<const uint32_t*>(scores), keys, idx, nan_count);
-  const int se = launch_radix_sort(keys, idx, skeys, sidx, n, 32, sort_ws, radix_sort_ws_bytes(n), st);
-  if (se != 0) return se;
   IsoArgs<T> a{};
-  a.n = n, a.ntiles = l.ntiles, a.npt = n + 1, a.ntl = l.ntl;
-  a.labels = labels, a.weights = weights, a.skeys = skeys, a.sidx = sidx;
-  a.sv = reinterpret_cast<uint32_t*>(ws + l.sv);
-  a.cW = reinterpret_cast<T*>(ws + l.cw), a.cY = reinterpret_cast<T*>(ws + l.cy);
-  a.tile_w = tiles, a.tile_y = tiles + l.ntiles, a.base_w = tiles + 2 * (size_t)l.ntiles;
-  a.base_y = tiles + 3 * (size_t)l.ntiles;
-  a.tot = misc, a.nan_count = nan_count, a.sort_err = radix_sort_error(sort_ws, n);
-  a.blo = reinterpret_cast<float*>(ws + l.keys), a.bhi = reinterpret_cast<float*>(ws + l.idx);
+  const int se = launch_score_prefix<T, IsoChannels>(scores, labels, weights, n, ws, l.p, ws + l.sort, st, a);
+  if (se != 0) return se;
+  a.npt = n + 1, a.ntl = l.ntl;
+  a.blo = reinterpret_cast<float*>(ws + l.p.keys), a.bhi = reinterpret_cast<float*>(ws + l.p.idx);
   a.bW = reinterpret_cast<T*>(ws + l.bw), a.bY = reinterpret_cast<T*>(ws + l.by);
   a.bv = reinterpret_cast<double*>(ws + l.bv);
   a.fitted = fitted, a.out = static_cast<T*>(out);
-  hipLaunchKernelGGL(iso_tile_kernel<T>, dim3(l.ntiles), dim3(kBlock), 0, st, a);
-  hipLaunchKernelGGL(iso_base_kernel<T>, dim3(1), dim3(kAucBaseThreads), 0, st, a);
-  hipLaunchKernelGGL(iso_cum_kernel<T>, dim3(l.ntiles), dim3(kBlock), 0, st, a);
   int* hull[2] = {reinterpret_cast<int*>(ws + l.hull_a), reinterpret_cast<int*>(ws + l.hull_b)};
   int* cnt[2] = {reinterpret_cast<int*>(ws + l.cnt_a), reinterpret_cast<int*>(ws + l.cnt_b)};
   hipLaunchKernelGGL(iso_leaf_kernel<T>, dim3(l.ntl), dim3(kBlock), 0, st, a, hull[0], cnt[0]);
@@ -374,9 +241,7 @@ static int launch_isotonic_t(const float* scores, const float* labels, const flo
 // 2^30.
 int launch_isotonic(const float* scores, const float* labels, const float* weights, int n, double* fitted, void* out,
                     void* ws, size_t ws_bytes, hipStream_t st) {
-  if (n < 1 || !scores || !labels || !out || !ws) return -1;
-  if ((reinterpret_cast<uintptr_t>(ws) & 15) || (reinterpret_cast<uintptr_t>(out) & 7)) return -1;  // (16-byte loads)
-  if ((unsigned)n > kOsCnt) return -5;
+  if (const int rc = metric_check_args(n, scores, labels, out, ws)) return rc;
   const IsoLayout l = iso_layout(n);
   if (ws_bytes < l.total) return -2;
   char* b = static_cast<char*>(ws);

@@ -26,6 +26,7 @@ using u64 = std::uintptr_t;
 #include "fm_explain.hip"
 #include "fm_topk.hip"
 #include "dedup.hip"
+#include "metric_common.hip"
 #include "auc.hip"
 #include "isotonic.hip"
 #include "gauc.hip"

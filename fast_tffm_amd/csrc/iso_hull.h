@@ -79,9 +79,6 @@ FM_ISO_HD void bridge(const Diagram<T>& d, const int* L, int nL, const int* R, i
   b = tangent(d, L[lo], R, nR);
 }
 
-// The fp32 score of an order-preserving key (hip/auc.hip auc_key; -0.0 was folded onto +0.0).
-FM_ISO_HD uint32_t key_to_bits(uint32_t key) { return (key & 0x80000000u) ? (key & 0x7fffffffu) : ~key; }
-
 // The block b of the ascending vertex list H[0 .. nH) that holds sorted position j: H[b] <= j < H[b + 1].
 FM_ISO_HD int block_of(const int* H, int nH, int j) {
   int lo = 0, hi = nH - 1;  // first index with H[index] > j, minus one

@@ -38,7 +38,7 @@ inline void for_each_col(int Kp, F&& f) {
 }
 
 // ---- the selection key ----------------------------------------------------------------------------
-// 64 bits: the score's order-preserving image (hip/auc.hip's map: negatives with all bits flipped, the
+// 64 bits: the score's order-preserving image (negatives with all bits flipped, the
 // others with the sign bit set) above 0xFFFFFFFF - candidate.  Greater key = greater score, equal scores
 // by ascending candidate; the k greatest keys are the answer.  Every key of a real candidate (< 2^31) is
 // nonzero, so 0 marks an empty place.

@@ -856,25 +856,41 @@ def fm_backward(dd: DedupOut, dpred: torch.Tensor, r1: torch.Tensor, Kp: int, *,
 # ---------------------------------------------------------------------------
 # validation metric: exact weighted ROC AUC
 # ---------------------------------------------------------------------------
-class AucStats:
+class _SortedScoreRecord:
+    """What the records of ``auc`` / ``gauc`` / ``isotonic_fit`` share: ``rec``, 64-bit words on the op's device
+    whose last one is the sort error word, and ``done``, the event behind the GPU launch chain on its stream
+    (None on the CPU, and for a chain captured into a graph: an event recorded into a graph cannot be waited
+    for, the reader synchronises with the replay)."""
+
+    __slots__ = ("rec", "weighted", "n", "done")
+    _op, _result = "", ""  # for the error message: the op's name, what there is none of
+
+    def __init__(self, rec: torch.Tensor, weighted: bool, n: int, done: "torch.cuda.Event | None" = None):
+        self.rec, self.weighted, self.n, self.done = rec, weighted, n, done
+
+    def _host_rec(self) -> torch.Tensor:
+        """The record on the host, once the chain has finished; raises on a nonzero sort error word."""
+        if self.done is not None:  # (the reader's current stream need not be the chain's)
+            self.done.synchronize()
+        r = self.rec.cpu()
+        err = int(r[-1])
+        if err:
+            raise RuntimeError(f"{self._op}: the radix sort's look-back spin bound was hit (error word {err}); "
+                               f"no {self._result} for this input")
+        return r
+
+
+class AucStats(_SortedScoreRecord):
     """The record of one ``auc`` call, on the op's device: ``[U2, P, N, NaN scores, sort error word]`` --
     int64 (unweighted: exact) or float64 (weighted).  ``stats()`` / ``value()`` read it (a host sync on
     the GPU) and raise when the GPU sort reported a failed look-back: never a number then."""
 
-    __slots__ = ("rec", "weighted", "n", "done")
-
-    def __init__(self, rec: torch.Tensor, weighted: bool, n: int, done: "torch.cuda.Event | None" = None):
-        self.rec, self.weighted, self.n = rec, weighted, n
-        self.done = done  # GPU: recorded behind the launch chain, on its stream
+    __slots__ = ()
+    _op, _result = "auc", "AUC"
 
     def stats(self) -> tuple:
         """(U2, P, N, nans) on the host: Python ints (unweighted) or floats and the int NaN count."""
-        if self.done is not None:  # (the reader's current stream need not be the chain's)
-            self.done.synchronize()
-        u2, p, n, nans, err = self.rec.tolist()
-        if err:
-            raise RuntimeError(f"auc: the radix sort's look-back spin bound was hit (error word {int(err)}); "
-                               "no AUC for this input")
+        u2, p, n, nans, _ = self._host_rec().tolist()
         return u2, p, n, int(nans)
 
     def value(self) -> float:
@@ -886,6 +902,43 @@ class AucStats:
 
 
 _SORT_UNSTABLE: set = set()  # devices whose in-tree sort failed _sort_selfcheck
+
+
+def _sorted_score_inputs(op: str, scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None,
+                         groups: torch.Tensor | None = None) -> tuple:
+    """The input checks of ``auc`` / ``gauc`` / ``isotonic_fit``: fp32 vectors (int32 ``groups``) on one device,
+    one entry per score, fewer than 2^30 scores.  Returns (device, n, weighted, record dtype)."""
+    dev = scores.device
+    n = scores.numel()
+    _chk_vec(scores, torch.float32, n, "scores", dev)
+    _chk_vec(labels, torch.float32, n, "labels", dev)
+    _chk_vec(groups, torch.int32, n, "groups", dev)
+    _chk_vec(weights, torch.float32, n, "weights", dev)
+    _check(labels.numel() == n and (groups is None or groups.numel() == n)
+           and (weights is None or weights.numel() == n),
+           f"{op}: one label / {'' if groups is None else 'group / '}weight per score")
+    _check(n < 2**30, f"{op}: n must be < 2^30 (the radix sort's bound)")
+    weighted = weights is not None
+    return dev, n, weighted, torch.float64 if weighted else torch.int64
+
+
+def _sorted_score_launch(op: str, dev: torch.device, need: int, ws: torch.Tensor | None, launch) -> tuple:
+    """The GPU launch of those ops: the sort's self-check, the workspace (``need`` bytes; allocated when ``ws`` is
+    None), ``launch(ws)`` on the current stream.  Returns (ws, the event behind the chain on that stream -- None
+    while the stream is capturing: an event recorded into a graph cannot be waited for, the reader synchronises
+    with the replay)."""
+    _sort_selfcheck(dev)
+    if dev.index in _SORT_UNSTABLE:
+        raise RuntimeError(f"{op}: the in-tree radix sort failed its stability self-check on this device")
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _chk_vec(ws, torch.uint8, need, "ws", dev)
+    launch(ws)
+    if torch.cuda.is_current_stream_capturing():
+        return ws, None
+    done = torch.cuda.Event()
+    done.record(torch.cuda.current_stream(dev))
+    return ws, done
 
 
 def auc_workspace(n: int, device: torch.device) -> torch.Tensor:
@@ -904,35 +957,22 @@ def auc(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None
     infinities and denormals ordered as usual); NaN scores are counted and make the AUC NaN.
     Unweighted statistics are integers (exact, the same on GPU and CPU); weighted ones are fp64 sums in a
     fixed order (bitwise the same run to run).  GPU: hip/auc.hip on the current stream (``ws``: reusable
-    ``auc_workspace``); CPU: a sort and one pass.  ``n == 0`` launches nothing (NaN).
+    ``auc_workspace``); CPU: a sort and one pass.  ``n == 0`` launches nothing (NaN).  With a caller's ``ws`` the
+    GPU chain can be captured into a graph (after one eager call on the device: the sort's self-check does not
+    run in a capture); the record of a captured call carries no event, so read it after synchronising with the
+    replay.
     """
-    dev = scores.device
-    n = scores.numel()
-    _chk_vec(scores, torch.float32, n, "scores", dev)
-    _chk_vec(labels, torch.float32, n, "labels", dev)
-    _chk_vec(weights, torch.float32, n, "weights", dev)
-    _check(labels.numel() == n and (weights is None or weights.numel() == n), "auc: one label / weight per score")
-    _check(n < 2**30, "auc: n must be < 2^30 (the radix sort's bound)")
-    weighted = weights is not None
+    dev, n, weighted, rdt = _sorted_score_inputs("auc", scores, labels, weights)
     if _DEBUG and weighted and n > 0 and not (scores.is_cuda and torch.cuda.is_current_stream_capturing()):
         _check(bool(weights.min() >= 0), "weights: must be >= 0")
-    rdt = torch.float64 if weighted else torch.int64
     if n == 0:
         return AucStats(torch.zeros(5, dtype=rdt), weighted, 0)  # (a host record: nothing is launched)
     rec = torch.empty(5, dtype=rdt, device=dev)
     if _is_gpu(scores):
         h = native.hip()
-        _sort_selfcheck(dev)
-        if dev.index in _SORT_UNSTABLE:
-            raise RuntimeError("auc: the in-tree radix sort failed its stability self-check on this device")
-        need = int(h.auc_workspace_bytes(n))
-        if ws is None:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        _chk_vec(ws, torch.uint8, need, "ws", dev)
-        h.auc(scores=_p(scores), labels=_p(labels), weights=_p(weights), n=n, out=_p(rec), ws=_p(ws),
-              ws_bytes=ws.numel(), stream=_stream(scores))
-        done = torch.cuda.Event()
-        done.record(torch.cuda.current_stream(dev))
+        _, done = _sorted_score_launch("auc", dev, int(h.auc_workspace_bytes(n)), ws, lambda w: h.auc(
+            scores=_p(scores), labels=_p(labels), weights=_p(weights), n=n, out=_p(rec), ws=_p(w),
+            ws_bytes=w.numel(), stream=_stream(scores)))
         return AucStats(rec, weighted, n, done)
     _check(ws is None, "auc: the workspace is a GPU argument")
     native.cpu().auc(n=n, scores=_p(scores), labels=_p(labels), weights=_p(weights), out=_p(rec))
@@ -942,30 +982,26 @@ def auc(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None
 # ---------------------------------------------------------------------------
 # validation metric: grouped AUC (GAUC)
 # ---------------------------------------------------------------------------
-class GaucStats:
+class GaucStats(_SortedScoreRecord):
     """The record of one ``gauc`` call, on the op's device: six 64-bit words ``[sum over the valid groups of
     W_g AUC_g (fp64), their sum of W_g, valid groups, examples in valid groups, NaN scores, sort error word]``
     (the sum of W_g is an integer without weights, fp64 with them) and ``groups``, the ``[G, 3]`` per-group
     ``(U2_g, P_g, N_g)`` (int64 / float64).  The readers synchronise with the launch chain on the GPU and raise
     when its sort reported a failed look-back: never a number then."""
 
-    __slots__ = ("rec", "groups", "weighted", "n", "num_groups", "done")
+    __slots__ = ("groups", "num_groups")
+    _op, _result = "gauc", "GAUC"
 
     def __init__(self, rec: torch.Tensor, groups: torch.Tensor, weighted: bool, n: int, num_groups: int,
                  done: "torch.cuda.Event | None" = None):
-        self.rec, self.groups, self.weighted, self.n, self.num_groups = rec, groups, weighted, n, num_groups
-        self.done = done  # GPU: recorded behind the launch chain, on its stream
+        super().__init__(rec, weighted, n, done)
+        self.groups, self.num_groups = groups, num_groups
 
     def stats(self) -> tuple:
         """(sum W AUC, sum W, valid groups, examples in valid groups, nans) on the host."""
-        if self.done is not None:  # (the reader's current stream need not be the chain's)
-            self.done.synchronize()
-        r = self.rec.cpu()
+        r = self._host_rec()
         f = r.view(torch.float64).tolist()
         i = r.tolist()
-        if i[5]:
-            raise RuntimeError(f"gauc: the radix sort's look-back spin bound was hit (error word {i[5]}); "
-                               "no GAUC for this input")
         return f[0], (f[1] if self.weighted else i[1]), i[2], i[3], i[4]
 
     def value(self) -> float:
@@ -1009,43 +1045,22 @@ def gauc(scores: torch.Tensor, labels: torch.Tensor, groups: torch.Tensor, num_g
     launches nothing (NaN).  Ids outside the range are an error with FM_DEBUG_CHECKS=1 and count as the last
     group without it.
     """
-    dev = scores.device
-    n = scores.numel()
     G = int(num_groups)
-    _chk_vec(scores, torch.float32, n, "scores", dev)
-    _chk_vec(labels, torch.float32, n, "labels", dev)
-    _chk_vec(groups, torch.int32, n, "groups", dev)
-    _chk_vec(weights, torch.float32, n, "weights", dev)
-    _check(labels.numel() == n and groups.numel() == n and (weights is None or weights.numel() == n),
-           "gauc: one label / group / weight per score")
-    _check(n < 2**30, "gauc: n must be < 2^30 (the radix sort's bound)")
+    dev, n, weighted, rdt = _sorted_score_inputs("gauc", scores, labels, weights, groups)
     _check(1 <= G < 2**31, "gauc: num_groups must be in [1, 2^31)")
-    weighted = weights is not None
     if _DEBUG and n > 0 and not (scores.is_cuda and torch.cuda.is_current_stream_capturing()):
         _check(bool(groups.min() >= 0) and bool(groups.max() < G), "groups: ids must be in [0, num_groups)")
         if weighted:
             _check(bool(weights.min() >= 0), "weights: must be >= 0")
-    rdt = torch.float64 if weighted else torch.int64
     if n == 0:  # (host records: nothing is launched)
         return GaucStats(torch.zeros(6, dtype=torch.int64), torch.zeros((G, 3), dtype=rdt), weighted, 0, G)
     rec = torch.empty(6, dtype=torch.int64, device=dev)
     per = torch.empty((G, 3), dtype=rdt, device=dev)
     if _is_gpu(scores):
         h = native.hip()
-        _sort_selfcheck(dev)
-        if dev.index in _SORT_UNSTABLE:
-            raise RuntimeError("gauc: the in-tree radix sort failed its stability self-check on this device")
-        need = int(h.gauc_workspace_bytes(n, G))
-        if ws is None:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        _chk_vec(ws, torch.uint8, need, "ws", dev)
-        h.gauc(scores=_p(scores), labels=_p(labels), weights=_p(weights), groups=_p(groups), n=n, G=G, out=_p(rec),
-               rec=_p(per), ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(scores))
-        if torch.cuda.is_current_stream_capturing():
-            # (an event recorded into a graph cannot be waited for: the reader synchronises with the replay)
-            return GaucStats(rec, per, weighted, n, G)
-        done = torch.cuda.Event()
-        done.record(torch.cuda.current_stream(dev))
+        _, done = _sorted_score_launch("gauc", dev, int(h.gauc_workspace_bytes(n, G)), ws, lambda w: h.gauc(
+            scores=_p(scores), labels=_p(labels), weights=_p(weights), groups=_p(groups), n=n, G=G, out=_p(rec),
+            rec=_p(per), ws=_p(w), ws_bytes=w.numel(), stream=_stream(scores)))
         return GaucStats(rec, per, weighted, n, G, done)
     _check(ws is None, "gauc: the workspace is a GPU argument")
     native.cpu().gauc(n=n, G=G, scores=_p(scores), labels=_p(labels), weights=_p(weights), groups=_p(groups),
@@ -1056,7 +1071,7 @@ def gauc(scores: torch.Tensor, labels: torch.Tensor, groups: torch.Tensor, num_g
 # ---------------------------------------------------------------------------
 # calibration: exact isotonic regression of (score, label, weight)
 # ---------------------------------------------------------------------------
-class IsotonicFit:
+class IsotonicFit(_SortedScoreRecord):
     """The record of one ``isotonic_fit`` call, on the op's device: ``[blocks, total weight, positive weight,
     NaN scores, sort error word]`` -- int64 (unweighted: exact) or float64 (weighted) -- and the block arrays.
     The readers (``count`` / ``totals`` / ``blocks`` / ``fitted`` / ``calibrator``) read the record (a host
@@ -1064,23 +1079,20 @@ class IsotonicFit:
     failed look-back.  On the GPU the block arrays live in the call's workspace: read them before the
     workspace is used again (``blocks`` copies)."""
 
-    __slots__ = ("rec", "weighted", "n", "done", "arrays", "fit", "keep", "scores", "_head")
+    __slots__ = ("arrays", "fit", "keep", "scores", "_head")
+    _op, _result = "isotonic_fit", "fit"
 
     def __init__(self, rec: torch.Tensor, weighted: bool, n: int, arrays: tuple | None = None,
                  fit: torch.Tensor | None = None, done: "torch.cuda.Event | None" = None,
                  keep: torch.Tensor | None = None, scores: torch.Tensor | None = None):
-        self.rec, self.weighted, self.n, self.arrays, self.fit, self.done = rec, weighted, n, arrays, fit, done
+        super().__init__(rec, weighted, n, done)
+        self.arrays, self.fit = arrays, fit
         self.keep, self.scores = keep, scores  # zero-weight examples were dropped: the mask, every score
         self._head = None
 
     def _read(self) -> tuple:
         if self._head is None:
-            if self.done is not None:
-                self.done.synchronize()
-            m, w, y, nans, err = self.rec.tolist()
-            if err:
-                raise RuntimeError(f"isotonic_fit: the radix sort's look-back spin bound was hit (error word "
-                                   f"{int(err)}); no fit for this input")
+            m, w, y, nans, _ = self._host_rec().tolist()
             if nans:
                 raise ValueError(f"isotonic_fit: {int(nans)} NaN score(s); there is no fit")
             self._head = (int(m), w, y)
@@ -1151,15 +1163,7 @@ def isotonic_fit(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tens
     GPU: hip/isotonic.hip on the current stream (``ws``: reusable ``isotonic_workspace``); CPU: a sort and the
     serial stack.  ``n == 0`` or no weight at all launches nothing and has no blocks.
     """
-    dev = scores.device
-    n = scores.numel()
-    _chk_vec(scores, torch.float32, n, "scores", dev)
-    _chk_vec(labels, torch.float32, n, "labels", dev)
-    _chk_vec(weights, torch.float32, n, "weights", dev)
-    _check(labels.numel() == n and (weights is None or weights.numel() == n),
-           "isotonic_fit: one label / weight per score")
-    _check(n < 2**30, "isotonic_fit: n must be < 2^30 (the radix sort's bound)")
-    weighted = weights is not None
+    dev, n, weighted, rdt = _sorted_score_inputs("isotonic_fit", scores, labels, weights)
     keep = all_scores = None
     if weighted and n > 0:
         _check(bool((weights >= 0).all()), "weights: must be >= 0")  # (NaN weights fail too)
@@ -1168,7 +1172,6 @@ def isotonic_fit(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tens
             keep, all_scores = pos, scores
             scores, labels, weights = scores[pos].contiguous(), labels[pos].contiguous(), weights[pos].contiguous()
             n = scores.numel()
-    rdt = torch.float64 if weighted else torch.int64
     if n == 0:  # (a host record: nothing is launched)
         fit = torch.empty(0, dtype=torch.float64, device=dev) if want_fitted else None
         return IsotonicFit(torch.zeros(5, dtype=rdt), weighted, 0, None, fit, None, keep, all_scores)
@@ -1176,17 +1179,9 @@ def isotonic_fit(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tens
     fit = torch.empty(n, dtype=torch.float64, device=dev) if want_fitted else None
     if _is_gpu(scores):
         h = native.hip()
-        _sort_selfcheck(dev)
-        if dev.index in _SORT_UNSTABLE:
-            raise RuntimeError("isotonic_fit: the in-tree radix sort failed its stability self-check on this device")
-        need = int(h.isotonic_workspace_bytes(n))
-        if ws is None:
-            ws = torch.empty(need, dtype=torch.uint8, device=dev)
-        _chk_vec(ws, torch.uint8, need, "ws", dev)
-        h.isotonic(scores=_p(scores), labels=_p(labels), weights=_p(weights), n=n, fitted=_p(fit), out=_p(rec),
-                   ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(scores))
-        done = torch.cuda.Event()
-        done.record(torch.cuda.current_stream(dev))
+        ws, done = _sorted_score_launch("isotonic_fit", dev, int(h.isotonic_workspace_bytes(n)), ws, lambda w: (
+            h.isotonic(scores=_p(scores), labels=_p(labels), weights=_p(weights), n=n, fitted=_p(fit), out=_p(rec),
+                       ws=_p(w), ws_bytes=w.numel(), stream=_stream(scores))))
         off = h.isotonic_block_offsets(n)
         dts = (torch.float32, torch.float32, rdt, rdt, torch.float64)
         arrays = tuple(ws[o:o + n * d.itemsize].view(d) for o, d in zip(off, dts))

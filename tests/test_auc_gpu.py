@@ -96,6 +96,29 @@ def test_non_default_stream():
     assert a.stats() == oracle_stats(s, y) and b.stats() == oracle_stats(s, y, w)
 
 
+@pytest.mark.parametrize("weighted", [False, True], ids=["unweighted", "weighted"])
+def test_graph_replay_on_new_scores_equals_eager(weighted):
+    n = 2 * 2048 + 77  # two full tiles of the prefix chain and a partial one
+    s, y, w = make_case(n, 21, weights="real" if weighted else None)
+    dev = torch.device("cuda")
+    ts, ty, tw = _t(np.round(16 * s) / 16, dev), _t(y, dev), _t(w, dev)  # (sixteenths: tie runs cross tile borders)
+    ws = K.auc_workspace(n, dev)
+    K.auc(ts, ty, tw, ws=ws).stats()  # (warm: the sort's one-time self-check does not run in a capture)
+    torch.cuda.synchronize()
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        st = K.auc(ts, ty, tw, ws=ws)
+    s2 = np.round(16 * np.random.default_rng(22).standard_normal(n)).astype(np.float32) / 16
+    ts.copy_(_t(s2, dev))
+    graph.replay()
+    torch.cuda.synchronize()
+    eager = K.auc(_t(s2, dev), ty, tw)
+    assert st.stats() == eager.stats()
+    assert torch.equal(st.rec.cpu().view(torch.int64), eager.rec.cpu().view(torch.int64))  # (fp64: bit for bit)
+    if not weighted:
+        assert st.stats() == K.auc(_t(s2, "cpu"), _t(y, "cpu")).stats() == oracle_stats(s2, y)
+
+
 def test_one_class_and_nan_scores():
     n = 8193
     s, y, _ = make_case(n, 8)

@@ -81,7 +81,7 @@ def kernel_shares(fn, calls: int = 5) -> str:
             continue
         name = ev.key
         kind = ("sort" if "os_" in name or "rs_" in name else
-                name.split("<")[0].split("(")[0].split("::")[-1] if "gauc_" in name or "auc_" in name else "other")
+                name.split("<")[0].split("(")[0].split("::")[-1] if "auc_" in name or "prefix_" in name else "other")
         buckets[kind] = buckets.get(kind, 0.0) + t
     total = sum(buckets.values()) or 1.0
     per_call = total / calls / 1000.0
