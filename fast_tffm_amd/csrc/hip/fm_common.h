@@ -509,6 +509,53 @@ __device__ inline float across_groups_sum(float v) {
   return v;
 }
 
+// ---- the same butterflies without the LDS crossbar ---------------------------
+// v + (v of lane ^ O), all 64 lanes active.  __shfl_xor is a ds_bpermute_b32 behind an s_waitcnt
+// lgkmcnt; the steps below are VALU cross-lane operations instead: DPP inside a 16-lane row (folded
+// into the add: v_add_f32_dpp), gfx950's permlane swaps between rows.  gfx9 DPP has no xor-4
+// pattern: that step stays a shuffle.  Float add is commutative, so a sum that pairs the same lanes
+// in the same order of steps has the bits of the shuffle butterfly.
+template <int O>
+__device__ inline float xor_add(float v) {
+  static_assert(O == 1 || O == 2 || O == 4 || O == 8 || O == 16 || O == 32, "xor butterfly step");
+  if constexpr (O == 32 || O == 16) {
+    // both operands v: one result holds the lower half's (O = 16: the even rows') value in both
+    // lanes of a pair, the other the upper's -- their sum is v + partner in every lane
+    const uint32_t u = __float_as_uint(v);
+    if constexpr (O == 32) {
+      const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
+      return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    } else {
+      const auto r = __builtin_amdgcn_permlane16_swap(u, u, false, false);
+      return __uint_as_float(r[0]) + __uint_as_float(r[1]);
+    }
+  } else if constexpr (O == 4) {
+    return v + __shfl_xor(v, 4, kWave);
+  } else {
+    // row_ror:8 | quad_perm:[2,3,0,1] | quad_perm:[1,0,3,2]
+    constexpr int ctrl = O == 8 ? 0x128 : O == 2 ? 0x4E : 0xB1;
+    return v + __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), ctrl, 0xf, 0xf, false));
+  }
+}
+
+template <int O>
+__device__ inline float xor_add_down(float v) {  // steps O, O / 2, ..., 1: group_sum's order
+  if constexpr (O >= 1) return xor_add_down<O / 2>(xor_add<O>(v));
+  else return v;
+}
+template <int O>
+__device__ inline float xor_add_up(float v) {  // steps O, 2 O, ..., 32: across_groups_sum's order
+  if constexpr (O < kWave) return xor_add_up<O * 2>(xor_add<O>(v));
+  else return v;
+}
+
+// group_sum / across_groups_sum with the pairing of the shuffle forms: bitwise the same sums.
+// Every lane of the wave must be active.
+template <int WIDTH>
+__device__ inline float group_sum_x(float v) { return xor_add_down<WIDTH / 2>(v); }
+template <int LPR>
+__device__ inline float across_groups_sum_x(float v) { return xor_add_up<LPR>(v); }
+
 __device__ inline float softplus_neg_abs(float p) {  // log(1 + exp(-|p|))
   return log1pf(__expf(-fabsf(p)));
 }

@@ -5,10 +5,14 @@
 // tffm/fm_model.py:311-333.
 //
 // Design: one wave64 per example; the example's (row, value) pairs are loaded
-// once, lane-parallel, and broadcast with ds_bpermute; factor rows are fetched
+// once, lane-parallel, and broadcast with ds_bpermute (batches without values
+// broadcast the rows only: the *_nox instantiations); factor rows are fetched
 // 16 B per lane, G = 64/LPR rows per wave instruction, UNR row groups in flight
 // per lane; r1 = sum x*v is cached for the backward (the reference recomputes
-// it, G5) and the loss gradient dpred is emitted by the same kernel (T6).
+// it, G5).  The example's sums are DPP / permlane-swap butterflies (no LDS
+// crossbar but for the xor-4 step).  Its pred is parked in a lane of the wave;
+// every 64 examples the wave stores the parked preds and computes their losses
+// and the loss gradient dpred lane-parallel (T6: emitted by the same kernel).
 #include "fm_common.h"
 
 namespace fm {
@@ -144,6 +148,51 @@ constexpr int fwd_unroll() {
                      : FwdUnroll<kWave / LPR>::v;
 }
 
+// Per-example overhead, each a compile-time select per instantiation (the A/Bs are in
+// profiles/r7/fwd_overhead.txt):
+//  * fwd_x_sums: the example's reductions as DPP / permlane-swap butterflies (fm_common.h xor_add)
+//    instead of ds_bpermute shuffles -- the same pairing, the same bits;
+//  * fwd_park_loss: the loss / dpred chain once per 64 examples of a wave, lane-parallel, instead of
+//    once per example with one lane active;
+//  * fwd_nox: batches without values (vals == nullptr, x = 1 everywhere) take instantiations without
+//    the per-row-slot broadcast of x and the multiply by it (slots past the example masked by select).
+// fp32 tables take all three; bf16 and fp8 tables keep the old paths.  The forward's results stay bit
+// for bit what they were, and they hang on which of the row loop's multiply-adds hipcc contracts into
+// FMAs.  For fp32 rows it contracts every one (the all-ones-x loop spells its FMA out), and the new
+// paths leave that alone.  For bf16 and fp8 rows the choice differs from one unrolled slot to the next
+// and moved when the code around the loop changed, so those instantiations are left instruction for
+// instruction what they were (checked on the assembly: profiles/r7/fwd_overhead.txt).
+template <int LPR, typename TV, bool SH>
+constexpr bool fwd_x_sums() { return std::is_same<TV, float>::value; }
+template <int LPR, typename TV, bool SH>
+constexpr bool fwd_park_loss() { return std::is_same<TV, float>::value; }
+template <int LPR, typename TV, bool SH>
+constexpr bool fwd_nox() { return std::is_same<TV, float>::value; }
+
+template <bool X, int WIDTH>
+__device__ __forceinline__ float fwd_group_sum(float v) {
+  if constexpr (X) return group_sum_x<WIDTH>(v);
+  else return group_sum<WIDTH>(v);
+}
+template <bool X, int LPR>
+__device__ __forceinline__ float fwd_across_sum(float v) {
+  if constexpr (X) return across_groups_sum_x<LPR>(v);
+  else return across_groups_sum<LPR>(v);
+}
+
+// Loss and dL/dpred of one example (dpred before the grad_scale factor).
+__device__ __forceinline__ void fwd_loss(int loss_type, float pred, float y, float wt, float& l, float& d) {
+  if (loss_type == kLossMse) {
+    const float diff = pred - y;
+    l = wt * diff * diff;
+    d = 2.f * wt * diff;
+  } else {
+    // sigmoid_cross_entropy_with_logits, numerically stable form
+    l = wt * (fmaxf(pred, 0.f) - pred * y + softplus_neg_abs(pred));
+    d = wt * (sigmoidf(pred) - y);
+  }
+}
+
 // SH: the row-sharded step's features -- rows[] may be keys (segment lookup), an occurrence's row
 // lives either in the gathered wire buffer (segment u) or, for this rank's own rows, in the table
 // (SelfRows).  Both instantiations share the mechanics measured on the local step: the example's
@@ -154,9 +203,12 @@ constexpr int fwd_unroll() {
 // group); the sharded one resolves each occurrence's row to a byte address once, lane-parallel
 // (source select, segment lookup, tail loads), and broadcasts the 64-bit address (two ds_bpermute
 // and one 64-bit add per row group) -- no per-row-group tag test or base / stride select.
-template <int LPR, typename TV, bool SH>
+// NOX: the batch carries no values (a.vals == nullptr): x = 1 for every occurrence.
+template <int LPR, typename TV, bool SH, bool NOX>
 __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
   using F = Frag<TV>;
+  constexpr bool kX = fwd_x_sums<LPR, TV, SH>();
+  constexpr bool kPark = fwd_park_loss<LPR, TV, SH>();
   constexpr int EPL = F::N;
   constexpr int G = kWave / LPR;
   constexpr int UNR = fwd_unroll<LPR, TV, SH>();
@@ -201,8 +253,29 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
     x = 0.f;
     if (lane < m) {
       row = a.rows[base + lane];
-      x = a.vals ? a.vals[base + lane] : 1.f;
+      x = !NOX && a.vals ? a.vals[base + lane] : 1.f;
     }
+  };
+  // (kPark) pred of the wave's n-th example waits in lane n & 63; after 64 examples, and once after
+  // the loop, every lane stores its example's pred, loads its label / weight and computes its loss and
+  // dpred -- the scalar expressions of the per-example form, 64 examples per issue instead of one.
+  // loss_acc takes the losses in example order (a readlane loop), so the workgroup's partial keeps
+  // its bits.
+  float park = 0.f;
+  int n_done = 0;  // examples of this wave so far
+  auto flush = [&](int n0, int cnt) {
+    float l = 0.f;
+    if (lane < cnt) {
+      const int ii = wave + (n0 + lane) * nwaves;
+      a.pred[ii] = park;
+      if (a.loss_type != kLossNone) {
+        float d;
+        fwd_loss(a.loss_type, park, a.labels[ii], a.weights ? a.weights[ii] : 1.f, l, d);
+        if (a.dpred) a.dpred[ii] = d * a.grad_scale;
+      }
+    }
+    if (a.loss_type != kLossNone)
+      for (int j = 0; j < cnt; ++j) loss_acc += __int_as_float(__builtin_amdgcn_readlane(__float_as_int(l), j));
   };
   int s = 0, e = 0, sn = 0, en = 0;
   int p_row = 0;
@@ -228,7 +301,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
     }
     // label / weight of example i: needed after the reduction, loaded now
     float y_pre = 0.f, wt_pre = 1.f;
-    if (kPrefetch && a.loss_type != kLossNone && lane == 0) {
+    if (!kPark && kPrefetch && a.loss_type != kLossNone && lane == 0) {
       y_pre = a.labels[i];
       if (a.weights) wt_pre = a.weights[i];
     }
@@ -288,7 +361,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
       }
 
       for (int q = 0; q < m; q += G * UNR) {
-        float fr[UNR][EPL], fx[UNR], fs[UNR];
+        float fr[UNR][EPL], fx[NOX ? 1 : UNR], fs[UNR];  // (fx: unused without values)
         int fraw[kRaw ? UNR : 1];
         // Issue every row load of the round before the first use.  Loads are unconditional (slots
         // past the example read a valid row -- lanes past it hold row 0 / lane 0's row -- and are
@@ -298,8 +371,10 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
         for (int u = 0; u < UNR; ++u) {
           const int f = q + u * G + g;
           const int fb = (f & (kWave - 1)) << 2;
-          const float x = __int_as_float(__builtin_amdgcn_ds_bpermute(fb, __float_as_int(my_x)));
-          fx[u] = f < m ? x : 0.f;
+          if constexpr (!NOX) {
+            const float x = __int_as_float(__builtin_amdgcn_ds_bpermute(fb, __float_as_int(my_x)));
+            fx[u] = f < m ? x : 0.f;
+          }
           if constexpr (SH) {
             // one broadcast per row group: the tagged row, then its source's base and stride (the
             // 64-bit address in two broadcasts: k16 bf16 0.525 -> 0.518 ms, k128 fp8 0.864 -> 0.857,
@@ -324,12 +399,24 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
           // reg term as a per-occurrence sum times scale^2 -- fewer VALU ops -- made the k128 fp8
           // FTRL step slower, 0.888 -> 1.014 ms same-box: profiles/r4/specialize_ab.txt)
           if constexpr (kRaw) F::cvt_scaled(fraw[u], fs[u], fv);
-          const float xm = fx[u] * tmask;
+          if constexpr (NOX) {
+            // x = 1: the slot's values themselves, or 0 past the example / the row; s2 as the FMA that the
+            // general loop's xv * xv + s2 is contracted to
+            const bool on = tact && (q + u * G + g) < m;
 #pragma unroll
-          for (int k = 0; k < EPL; ++k) {
-            const float xv = xm * fv[k];
-            s1[k] += xv;
-            if constexpr (!kNorm) s2[k] += xv * xv;
+            for (int k = 0; k < EPL; ++k) {
+              const float xv = on ? fv[k] : 0.f;
+              s1[k] += xv;
+              if constexpr (!kNorm) s2[k] = __builtin_fmaf(xv, xv, s2[k]);
+            }
+          } else {
+            const float xm = fx[u] * tmask;
+#pragma unroll
+            for (int k = 0; k < EPL; ++k) {
+              const float xv = xm * fv[k];
+              s1[k] += xv;
+              if constexpr (!kNorm) s2[k] += xv * xv;
+            }
           }
           if (!kNorm && want_reg) {
             const float ok = (q + u * G + g) < m ? 1.f : 0.f;
@@ -349,45 +436,47 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
     float part = 0.f;
 #pragma unroll
     for (int k = 0; k < EPL; ++k) {
-      s1[k] = across_groups_sum<LPR>(s1[k]);
-      s2[k] = across_groups_sum<LPR>(s2[k]);
+      s1[k] = fwd_across_sum<kX, LPR>(s1[k]);
+      s2[k] = fwd_across_sum<kX, LPR>(s2[k]);
       part += s1[k] * s1[k] - s2[k];
     }
-    part = group_sum<LPR>(part);
-    if constexpr (kNorm) part -= group_sum<kWave>(s2n);
-    lin = group_sum<kWave>(lin);
+    part = fwd_group_sum<kX, LPR>(part);
+    if constexpr (kNorm) part -= fwd_group_sum<kX, kWave>(s2n);
+    lin = fwd_group_sum<kX, kWave>(lin);
     const float pred = lin + 0.5f * part + (a.bias ? a.bias[0] : 0.f);
     if (a.r1 != nullptr && g == 0 && tact) store_r1<TV, EPL>(a.r1, (long long)i * a.Kp + t * EPL, s1);
     if (want_reg) {
-      rv = group_sum<kWave>(rv);
-      rw = group_sum<kWave>(rw);
+      rv = fwd_group_sum<kX, kWave>(rv);
+      rw = fwd_group_sum<kX, kWave>(rw);
       regv_acc += rv;
       regw_acc += rw;
     }
     // loss and dL/dpred (every lane holds the same pred: butterfly sums are lane-symmetric)
-    float l = 0.f, d = 0.f;
-    if (a.loss_type != kLossNone && lane == 0) {
-      const float y = kPrefetch ? y_pre : a.labels[i];
-      const float wt = kPrefetch ? wt_pre : (a.weights ? a.weights[i] : 1.f);
-      if (a.loss_type == kLossMse) {
-        const float diff = pred - y;
-        l = wt * diff * diff;
-        d = 2.f * wt * diff;
-      } else {
-        // sigmoid_cross_entropy_with_logits, numerically stable form
-        l = wt * (fmaxf(pred, 0.f) - pred * y + softplus_neg_abs(pred));
-        d = wt * (sigmoidf(pred) - y);
+    if constexpr (kPark) {
+      if (lane == (n_done & (kWave - 1))) park = pred;
+      ++n_done;
+      if ((n_done & (kWave - 1)) == 0) flush(n_done - kWave, kWave);
+    } else {
+      float l = 0.f, d = 0.f;
+      if (a.loss_type != kLossNone && lane == 0) {
+        const float y = kPrefetch ? y_pre : a.labels[i];
+        const float wt = kPrefetch ? wt_pre : (a.weights ? a.weights[i] : 1.f);
+        fwd_loss(a.loss_type, pred, y, wt, l, d);
       }
-    }
-    if (lane == 0) {
-      a.pred[i] = pred;
-      if (a.loss_type != kLossNone) {
-        loss_acc += l;
-        if (a.dpred) a.dpred[i] = d * a.grad_scale;
+      if (lane == 0) {
+        a.pred[i] = pred;
+        if (a.loss_type != kLossNone) {
+          loss_acc += l;
+          if (a.dpred) a.dpred[i] = d * a.grad_scale;
+        }
       }
     }
     s = sn; e = en; sn = snn; en = enn;
     p_row = n_row; p_x = n_x;
+  }
+  if constexpr (kPark) {
+    const int n_all = __builtin_amdgcn_readfirstlane(n_done);
+    if (n_all & (kWave - 1)) flush(n_all & ~(kWave - 1), n_all & (kWave - 1));
   }
   if (a.loss_partial == nullptr && a.reg_partial == nullptr) return;
   __shared__ float red[3][kWavesPerBlock];
@@ -408,14 +497,25 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
 template <int LPR, typename TV>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(fwd_local_min_waves<LPR, TV>())))
 void fm_fwd_kernel(FwdArgs a) {
-  fwd_body<LPR, TV, false>(a);
+  fwd_body<LPR, TV, false, false>(a);
+}
+// fp32 batches without values (launch_fwd: a.vals == nullptr)
+template <int LPR, typename TV>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(fwd_local_min_waves<LPR, TV>())))
+void fm_fwd_kernel_nox(FwdArgs a) {
+  fwd_body<LPR, TV, false, fwd_nox<LPR, TV, false>()>(a);
 }
 
 // The row-sharded step's forward (self rows, segment lookup).
 template <int LPR, typename TV>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(fwd_local_min_waves<LPR, TV, true>())))
 void fm_fwd_shard_kernel(FwdArgs a) {
-  fwd_body<LPR, TV, true>(a);
+  fwd_body<LPR, TV, true, false>(a);
+}
+template <int LPR, typename TV>
+__global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(fwd_local_min_waves<LPR, TV, true>())))
+void fm_fwd_shard_kernel_nox(FwdArgs a) {
+  fwd_body<LPR, TV, true, fwd_nox<LPR, TV, true>()>(a);
 }
 
 // The matrix-core form of the fp8 k=128 forward is a build variant ("mfma": -DFM_WITH_MFMA=1), not part
@@ -496,11 +596,37 @@ int launch_fwd(const FwdArgs& a, int dtype, int grid, hipStream_t st) {
   }
 #endif
 
+  // all-ones x (fp32 rows, fwd_nox): no broadcast of x, no multiply by it
+  const bool nox = a.vals == nullptr && dtype == kF32;
   if (a.self.u1 > a.self.u0 || a.seg_idx || !FM_FWD_SPECIALIZE || !table_rows) {
-    FM_DISPATCH(dtype, lpr, fm_fwd_shard_kernel, grid, st, a);
+    if (nox) { FM_DISPATCH_LPR(lpr, fm_fwd_shard_kernel_nox, float, grid, 0, st, a); }
+    else { FM_DISPATCH(dtype, lpr, fm_fwd_shard_kernel, grid, st, a); }
   } else {
-    FM_DISPATCH(dtype, lpr, fm_fwd_kernel, grid, st, a);
+    if (nox) { FM_DISPATCH_LPR(lpr, fm_fwd_kernel_nox, float, grid, 0, st, a); }
+    else { FM_DISPATCH(dtype, lpr, fm_fwd_kernel, grid, st, a); }
   }
+  return (int)hipGetLastError();
+}
+
+// Test entry point (tests/test_fwd_overhead_gpu.py): out[4][6][n] = the shuffle sums and the DPP /
+// permlane sums of x, wave by wave -- group_sum widths 2..64, then across-groups sums of group widths
+// 1..32.  n = 64 * waves.
+template <int I>
+__device__ inline void reduce_probe_store(float v, float* out, int n, int idx) {
+  constexpr int W = 2 << I, L = 1 << I;
+  out[(0 * 6 + I) * (long long)n + idx] = group_sum<W>(v);
+  out[(1 * 6 + I) * (long long)n + idx] = group_sum_x<W>(v);
+  out[(2 * 6 + I) * (long long)n + idx] = across_groups_sum<L>(v);
+  out[(3 * 6 + I) * (long long)n + idx] = across_groups_sum_x<L>(v);
+  if constexpr (I < 5) reduce_probe_store<I + 1>(v, out, n, idx);
+}
+__global__ __launch_bounds__(kWave) void fwd_reduce_probe_kernel(const float* x, float* out, int n) {
+  const int idx = blockIdx.x * kWave + threadIdx.x;
+  reduce_probe_store<0>(x[idx], out, n, idx);
+}
+int launch_fwd_reduce_probe(const float* x, int waves, float* out, hipStream_t st) {
+  if (waves <= 0) return 0;
+  hipLaunchKernelGGL(fwd_reduce_probe_kernel, dim3(waves), dim3(kWave), 0, st, x, out, waves * kWave);
   return (int)hipGetLastError();
 }
 

@@ -128,6 +128,13 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       py::arg("self_rows") = std::vector<long long>{}, py::arg("seg_idx") = 0, py::arg("seg_keys") = 0,
       py::arg("seg_shift") = 0, py::arg("max_feats") = -1);
 
+  m.def(  // test entry point: shuffle sums and DPP / permlane sums side by side, out[4][6][64 * waves]
+      "fwd_reduce_probe",
+      [](u64 x, int waves, u64 out, u64 stream) {
+        check(fm::launch_fwd_reduce_probe(P<const float>(x), waves, P<float>(out), S(stream)), "fwd_reduce_probe");
+      },
+      py::arg("x"), py::arg("waves"), py::arg("out"), py::arg("stream"));
+
   m.def(
       "explain",  // exact per-occurrence attributions (fm_explain.hip): contrib[nnz], pred[B] = sum + bias
       [](int B, u64 offsets, u64 rows, u64 vals, u64 v, long long v_stride, u64 w, long long w_stride, int Kp,
