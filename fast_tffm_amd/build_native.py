@@ -31,10 +31,10 @@ ARCH = os.environ.get("FM_OFFLOAD_ARCH", "gfx950")
 
 CPU_SOURCES = ["cpu/module.cpp", "cpu/parser.cpp", "cpu/kernels.cpp", "cpu/loader.cpp", "cpu/bincsr.cpp"]
 HIP_SOURCES = ["hip/module.hip"]
-# A/B build variants of the gfx950 module: name -> preprocessor defines (module _fm_hip_<name>,
-# selected at run time with FM_HIP_VARIANT=<name>; tools/gpu_ab.sh).  Same-box kernel comparisons
-# of a change against its predecessor; a variant is deleted with the losing code path once the
-# A/B is recorded under profiles/ (round 1-2's nocap / unr* / fwdw* / fp8packed went that way).
+# Build variants of the gfx950 module: name -> preprocessor defines (module _fm_hip_<name>,
+# selected at run time with FM_HIP_VARIANT=<name>; tools/gpu_ab.sh).  Only "mfma" is kept; a same-box
+# A/B of a kernel change against its predecessor adds its variant on a branch, and the variant is
+# deleted with the losing code path once the A/B is recorded under profiles/.
 from fast_tffm_amd.build_variants import HIP_VARIANTS  # noqa: E402  (not hashed: flags are)
 
 

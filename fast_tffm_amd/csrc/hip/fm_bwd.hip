@@ -39,38 +39,22 @@ constexpr int kMaxPieceOwners = 64;  // owners of a split backward piece
 // r1 rows in flight per lane in the chunk kernel: 8 beat 4 / 6 (fewer VGPRs, more waves) and 12 /
 // 16 on k64 fp32, k64 bf16 and k128 fp8 in round 1 (profiles/r1s3/chunk_unroll_ab.txt); still the
 // best for k <= 64 with the round-4 kernels, but not for k = 128 (below)
-#ifndef FM_CHUNK_UNR
-#define FM_CHUNK_UNR 8
-#endif
-constexpr int kChunkUnr = FM_CHUNK_UNR;
-#ifndef FM_R1_MASK
-#define FM_R1_MASK 1
-#endif
-#ifndef FM_CHUNK_PERM
-#define FM_CHUNK_PERM 0
-#endif
+constexpr int kChunkUnr = 8;
 // The local kernels' 32-lane rows (k = 128): 12 r1 rows in flight per lane.  Same-box A/B
 // (profiles/r4/chunk_unr_ab.txt): k128 fp8 FTRL 0.874 -> 0.807 ms with 12, 0.856 with 16; 16-lane and
 // 4-lane rows (k64 / k16) lose with 12 or 16 (k64 fp32 0.615 -> 0.625-0.640), and so does the
-// row-sharded step's general kernel (k128 fp8 at world 1 1.121 -> 1.288 ms).  FM_CHUNK_UNR32 overrides.
-#ifndef FM_CHUNK_UNR32
-#define FM_CHUNK_UNR32 12
-#endif
-// The EMIT-specialised kernel of the row-sharded step: 12 for fp8 rows (bf16 r1 rows: half the
-// registers per row in flight); fp32 / bf16 rows spill 12 VGPRs at 12 under the 128-VGPR cap and
-// keep 8.  FM_CHUNK_UNR32_EMIT overrides the fp8 value.
-#ifndef FM_CHUNK_UNR32_EMIT
-#define FM_CHUNK_UNR32_EMIT FM_CHUNK_UNR32
-#endif
+// row-sharded step's general kernel (k128 fp8 at world 1 1.121 -> 1.288 ms).
+constexpr int kChunkUnr32 = 12;
+// The EMIT-specialised kernel of the row-sharded step: the same 12 for fp8 rows (bf16 r1 rows: half
+// the registers per row in flight); fp32 / bf16 rows spill 12 VGPRs at 12 under the 128-VGPR cap and
+// keep 8.
 // The wide fp8 kernel (8 values per lane, below): 5 r1 rows in flight per lane (6 spills 6 VGPRs under
-// the 128-VGPR cap, 4 one) -- about the bytes in flight of the 4-value kernel's 12.  FM_CHUNK_UNR_W8 overrides.
-#ifndef FM_CHUNK_UNR_W8
-#define FM_CHUNK_UNR_W8 5
-#endif
+// the 128-VGPR cap, 4 one) -- about the bytes in flight of the 4-value kernel's 12.
+constexpr int kChunkUnrW8 = 5;
 template <int LPR, bool LOC, bool EMT, typename TV>
 constexpr int chunk_unr() {
-  return LOC && LPR == 32 ? FM_CHUNK_UNR32
-         : EMT && LPR == 32 ? (R1Bf16<TV>::v ? FM_CHUNK_UNR32_EMIT : kChunkUnr)
+  return LOC && LPR == 32 ? kChunkUnr32
+         : EMT && LPR == 32 ? (R1Bf16<TV>::v ? kChunkUnr32 : kChunkUnr)
                             : kChunkUnr;
 }
 
@@ -152,11 +136,8 @@ __device__ inline void* state_row(void* s, long long row, long long stride) {
 // 4-value one) -- and the fused forms made the k = 128 bf16 FTRL step 1.025 -> 0.94 ms.  fp32 tables
 // keep the plain expressions: pinned, the row-sharded step's k = 64 fp32 EMIT kernels ran 0.620 ->
 // 0.666 ms (profiles/r6/fp8_wide_ab.txt); no wide fp32 kernel needs the pinned bits.
-#ifndef FM_FMA_PIN
-#define FM_FMA_PIN 1  // 0: plain expressions for every dtype (A/B build variant "nopin")
-#endif
 template <typename TV>
-constexpr bool fma_pinned() { return FM_FMA_PIN && !std::is_same<TV, float>::value; }
+constexpr bool fma_pinned() { return !std::is_same<TV, float>::value; }
 template <typename TV>
 __device__ __forceinline__ float row_grad(float A, float Scx, float nreg_v, float v) {
   if constexpr (fma_pinned<TV>()) return __builtin_fmaf(nreg_v, v, __builtin_fmaf(-Scx, v, A));
@@ -424,9 +405,6 @@ enum ChunkKind : int {
   kChunkAny = 0, kChunkLocal = 1, kChunkLocalNoX = 2,
   kChunkEmit = 3, kChunkEmitNoX = 4, kChunkEmitPc = 5, kChunkEmitPcNoX = 6
 };
-#ifndef FM_BWD_SPECIALIZE
-#define FM_BWD_SPECIALIZE 1  // 0: every mode runs kChunkAny (the "bwdgen" build variant, A/B)
-#endif
 
 // One lane group per chunk of <= CH (<= kMaxCH) sorted occurrences of one row.
 template <int LPR, typename TV, int KV, int EW = 0>
@@ -441,7 +419,7 @@ __device__ __forceinline__ void bwd_chunk_body(const BwdArgs& a) {
   static_assert(EW == 0 || LOC || EMT, "the wide kernels: local and EMIT kinds");
   constexpr int G = kWave / LPR;
   constexpr int PF = (kMaxCH + LPR - 1) / LPR;  // prefetched occurrences per lane
-  constexpr int UNR0 = EW ? FM_CHUNK_UNR_W8 : chunk_unr<LPR, LOC, EMT, TV>();
+  constexpr int UNR0 = EW ? kChunkUnrW8 : chunk_unr<LPR, LOC, EMT, TV>();
   constexpr int UNR = LPR < UNR0 ? LPR : UNR0;  // r1 rows in flight
   constexpr bool kShortPath = LPR * EPL >= 128;                   // short-chunk block (below): k = 128 rows
   const int lane = threadIdx.x & (kWave - 1);
@@ -462,11 +440,11 @@ __device__ __forceinline__ void bwd_chunk_body(const BwdArgs& a) {
   };
   // the r1 row of an occurrence slot only where the slot holds one (its c is 0 otherwise): the unused
   // slots of the 4-slot short block -- 275k of a Criteo-shaped batch's 378k rows occur once -- issue no
-  // load (FM_R1_MASK=0: every slot loads its lane's clamped row, the A/B).  Masking the UNR blocks'
-  // tails too was much slower (k64 fp32 0.592-0.597 -> 0.701-0.704 ms, EMIT 0.624 -> 0.736: each masked
+  // load (against every slot loading its lane's clamped row: profiles/r6/fp8_epilogue_ab.txt).  Masking
+  // the UNR blocks' tails too was much slower (k64 fp32 0.592-0.597 -> 0.701-0.704 ms, EMIT 0.624 -> 0.736: each masked
   // load became its own branch, so the block's loads no longer went out together; round 6).
   auto r1_at_if = [&](bool need, int ex, float (&o)[EPL]) {
-    if (!FM_R1_MASK || need) {
+    if (need) {
       r1_at(ex, o);
     } else {
 #pragma unroll
@@ -502,13 +480,6 @@ __device__ __forceinline__ void bwd_chunk_body(const BwdArgs& a) {
       while (q + 1 < a.n_owners && pr_pre[q + 1] <= i) ++q;
       return pr_start[q] + (i - pr_pre[q]);
     }
-#if FM_CHUNK_PERM
-    // (probe variant "chunkperm": the walk interleaves 8 far-apart streams of chunks -- lane groups
-    // working together reduce rows ~n/8 apart instead of consecutive ones -- to measure what the
-    // read-modify-write's page locality is worth: profiles/r6/rmw_locality.txt)
-    const int q8 = nchunks / 8;
-    if (i < 8 * q8) return (i & 7) * q8 + (i >> 3);
-#endif
     return i;
   };
   int c = ii < i1 ? chunk_at(ii) : 0;
@@ -682,7 +653,6 @@ void fm_bwd_chunk_local_kernel(BwdArgs a) { bwd_chunk_body<LPR, TV, kChunkLocal>
 template <int LPR, typename TV>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(chunk_min_waves<LPR, TV>())))
 void fm_bwd_chunk_local_nox_kernel(BwdArgs a) { bwd_chunk_body<LPR, TV, kChunkLocalNoX>(a); }
-#if FM_FP8_WIDE
 // the wide fp8 kernels (8 values per lane; LPR = Kp / 8): 128-VGPR cap as the 32-lane fp8 kernels
 template <int LPR>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4)))
@@ -690,7 +660,6 @@ void fm_bwd_chunk_local_w8_kernel(BwdArgs a) { bwd_chunk_body<LPR, fp8e4m3, kChu
 template <int LPR>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4)))
 void fm_bwd_chunk_local_nox_w8_kernel(BwdArgs a) { bwd_chunk_body<LPR, fp8e4m3, kChunkLocalNoX, 8>(a); }
-#endif
 #define FM_EMIT_CHUNK_KERNEL(NAME, KIND)                                                          \
   template <int LPR, typename TV>                                                                 \
   __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(chunk_min_waves<LPR, TV>()))) \
@@ -700,12 +669,10 @@ FM_EMIT_CHUNK_KERNEL(fm_bwd_chunk_emit_nox_kernel, kChunkEmitNoX)
 FM_EMIT_CHUNK_KERNEL(fm_bwd_chunk_emit_pc_kernel, kChunkEmitPc)
 FM_EMIT_CHUNK_KERNEL(fm_bwd_chunk_emit_pc_nox_kernel, kChunkEmitPcNoX)
 #undef FM_EMIT_CHUNK_KERNEL
-#if FM_FP8_WIDE
 // (the row-sharded step's wide fp8 kernels: wire / own-table rows, gradient rows or in-place own rows)
 template <int KIND>
 __global__ __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(4)))
 void fm_bwd_chunk_emit_w8_kernel(BwdArgs a) { bwd_chunk_body<16, fp8e4m3, KIND, 8>(a); }
-#endif
 
 // Rows split over 2..kSmallChunks chunks: one lane group, ordered sum of the partials (EW: the wide fp8
 // form, 8 values per lane -- the same sums in the same order).
@@ -844,14 +811,12 @@ __global__ __launch_bounds__(kBlock) void fm_bwd_combine_kernel(BwdArgs a) {
   if ((int)blockIdx.x < a.big_blocks) bwd_big_body<LPR, TV>(a, blockIdx.x, a.big_blocks, sr);
   else bwd_combine_body<LPR, TV>(a, blockIdx.x - a.big_blocks, gridDim.x - a.big_blocks, sr);
 }
-#if FM_FP8_WIDE
 // the lane-group combine of the wide fp8 rows (the hot-row workgroup combine keeps 4 values per lane: its
 // group count fixes the summation order)
 template <int LPR>
 __global__ __launch_bounds__(kBlock) void fm_bwd_combine_w8_kernel(BwdArgs a) {
   bwd_combine_body<LPR, fp8e4m3, 8>(a, blockIdx.x, gridDim.x, sr_step_seed(a.sr_counter));
 }
-#endif
 
 // specialised kinds (local / EMIT) share the launch shape: EMIT runs the local step's kernel body
 static bool fast_kind(int kind) { return kind != kChunkAny; }
@@ -860,6 +825,14 @@ static int chunk_wg_per_cu(int lpr, int kind) { return fast_kind(kind) && lpr <=
 
 static long long g_bwd_wide_launches = 0;  // (host counter: tests check the wide kernel ran)
 long long bwd_wide_launches() { return g_bwd_wide_launches; }
+// Test hook: false keeps fp8 rows on the 4-value kernels (the wide kernels' fallback and their bitwise
+// reference) in launch_bwd and launch_apply_runs (shard.hip); returns the previous setting.
+static bool g_fp8_wide = true;
+bool set_fp8_wide(bool on) {
+  const bool was = g_fp8_wide;
+  g_fp8_wide = on;
+  return was;
+}
 
 int launch_bwd(const BwdArgs& a, int dtype, long long max_chunks, long long max_unique, hipStream_t st) {
   if (max_chunks <= 0) return 0;
@@ -888,9 +861,9 @@ int launch_bwd(const BwdArgs& a, int dtype, long long max_chunks, long long max_
   // rows' launch, or both launches concurrent -- measured slower: k64 0.669 -> 0.72-0.78 ms, each
   // launch as long as the whole walk; profiles/r3/bwd_split_ab.txt)
   // specialised chunk kernels (see ChunkKind) when r1 fits 32-bit offsets: LOCAL mode, and EMIT mode
-  // (the row-sharded step; the "bwdgen" build variant keeps every mode on the general kernel, A/B)
+  // (the row-sharded step); every other case keeps the general kernel
   const long long r1_bytes = (long long)a.nex * a.Kp * (dtype == kFP8 ? 2 : 4);
-  const bool fits = FM_BWD_SPECIALIZE && lpr >= 4 && r1_bytes < (1LL << 32);
+  const bool fits = lpr >= 4 && r1_bytes < (1LL << 32);
   int kind = kChunkAny;
   if (fits && a.mode == kBwdLocal && a.piece < 0) {
     kind = a.sorted_x ? kChunkLocal : kChunkLocalNoX;
@@ -912,12 +885,10 @@ int launch_bwd(const BwdArgs& a, int dtype, long long max_chunks, long long max_
   // wide fp8 rows (k = 128, 16 lanes x 8 values): rows, r1 rows and state rows 16-byte aligned
   // (EMIT: wire rows and own table rows 8-byte aligned too)
   const bool emit_kind = kind >= kChunkEmit;
-  const bool wide = FM_FP8_WIDE && dtype == kFP8 && lpr == 32 && a.Kp % 8 == 0 && fast_kind(kind) &&
+  const bool wide = g_fp8_wide && dtype == kFP8 && lpr == 32 && a.Kp % 8 == 0 && fast_kind(kind) &&
                     a.v_stride % 8 == 0 && a.s_stride % 8 == 0 && ((uintptr_t)a.v % 8 == 0) &&
                     ((uintptr_t)a.r1 % 16 == 0) && ((uintptr_t)a.s0v % 16 == 0) && ((uintptr_t)a.s1v % 16 == 0) &&
                     (!emit_kind || (a.self.v_stride % 8 == 0 && (uintptr_t)a.self.v % 8 == 0));
-  (void)wide;
-#if FM_FP8_WIDE
   if (wide) {
     ++g_bwd_wide_launches;
     const int gw = (fill_grid(max_chunks, kWavesPerBlock * (kWave / 16), 8192) + 7) / 8 * 8;
@@ -941,9 +912,7 @@ int launch_bwd(const BwdArgs& a, int dtype, long long max_chunks, long long max_
         hipLaunchKernelGGL(fm_bwd_chunk_emit_w8_kernel<kChunkEmitPcNoX>, dim3(gw), dim3(kBlock), chunk_lds, st, a);
         break;
     }
-  } else
-#endif
-  if (kind == kChunkLocalNoX) {
+  } else if (kind == kChunkLocalNoX) {
     FM_DISPATCH_WIDE(dtype, lpr, fm_bwd_chunk_local_nox_kernel, g1, chunk_lds, st, a);
   } else if (kind == kChunkLocal) {
     FM_DISPATCH_WIDE(dtype, lpr, fm_bwd_chunk_local_kernel, g1, chunk_lds, st, a);
@@ -961,16 +930,12 @@ int launch_bwd(const BwdArgs& a, int dtype, long long max_chunks, long long max_
   BwdArgs b = a;
   if (lpr >= 32) {  // (one launch lost for 32-lane rows: above)
     b.big_blocks = 0;
-#ifndef FM_FP8_WIDE_COMBINE
-#define FM_FP8_WIDE_COMBINE 1  // (0: the 4-value lane-group combine beside the wide chunk kernel, A/B)
-#endif
-#if FM_FP8_WIDE
-    if (wide && FM_FP8_WIDE_COMBINE)
+    if (wide) {
       hipLaunchKernelGGL(fm_bwd_combine_w8_kernel<16>, dim3(fill_grid(max_unique, kWavesPerBlock * (kWave / 16), 2048)),
                          dim3(kBlock), 0, st, b);
-    else
-#endif
-    FM_DISPATCH(dtype, lpr, fm_bwd_combine_kernel, g2, st, b);
+    } else {
+      FM_DISPATCH(dtype, lpr, fm_bwd_combine_kernel, g2, st, b);
+    }
     b.big_blocks = kBigBlocks;
     FM_DISPATCH(dtype, lpr, fm_bwd_combine_kernel, kBigBlocks, st, b);
   } else {

@@ -66,18 +66,11 @@ __device__ inline uint32_t sr_next(uint32_t r) {
 // rounded expansions, and the stochastic-rounding words of a lane's 4 values as rotations of ONE
 // hash instead of a hash plus a 3-step xorshift chain (each rotation's bits are uniform on their
 // own, which is all an unbiased rounding needs).  The k128 fp8 FTRL chunk backward is VALU-bound
-// with its per-row epilogue as large as its occurrence loop (profiles/r6/fp8_epilogue_ab.txt).
-// FM_FP8_FAST_EPI=0 (build variant "fp8slow") keeps the exact forms: the A/B.
-#ifndef FM_FP8_FAST_EPI
-#define FM_FP8_FAST_EPI 1
-#endif
+// with its per-row epilogue as large as its occurrence loop (profiles/r6/fp8_epilogue_ab.txt: the
+// exact forms cost 5204 against 3749 VALU instructions per wave).
 __device__ inline uint32_t sr_rot(uint32_t x, int s) { return __builtin_amdgcn_alignbit(x, x, s); }
 // random word i (0..3) of a lane's 4 values from one hash
 __device__ inline uint32_t sr_word(uint32_t r0, int i) {
-  if (!FM_FP8_FAST_EPI) {
-    for (int k = 0; k < i; ++k) r0 = sr_next(r0);
-    return r0;
-  }
   return i == 0 ? r0 : sr_rot(r0, i == 1 ? 16 : i == 2 ? 8 : 24);
 }
 
@@ -459,15 +452,13 @@ __device__ inline void store_row_fp8x8(fp8e4m3* lane_ptr, const float (&o)[8], f
   }
 }
 
-// Wide fp8 kernels (FM_FP8_WIDE=1, default): k = 128 fp8 rows reduced / updated with 8 values per lane --
+// Wide fp8 kernels: k = 128 fp8 rows reduced / updated with 8 values per lane --
 // 8-byte row loads, 16-byte r1 / optimizer-state / bf16-gradient accesses, LPR = Kp / 8 -- instead of 4
 // (4-, 8- and 8-byte accesses): the same bytes with half the per-lane addresses, which the gather-bound
 // kernels spend their texture-address time on, and twice the rows per wave.  The chunk backward (local and
-// EMIT kinds) and the owner apply; bitwise the same results (store_row_fp8x8).  0 keeps the 4-value kernels
-// (the "fp8narrow" build variant, A/B).
-#ifndef FM_FP8_WIDE
-#define FM_FP8_WIDE 1
-#endif
+// EMIT kinds) and the owner apply; bitwise the same results (store_row_fp8x8).  The 4-value kernels stay
+// as the fallback where the launchers find the alignment conditions unmet, and as the wide kernels'
+// reference (set_fp8_wide(false), fm_bwd.hip: tests/test_fp8_wide_gpu.py).
 
 // EPL values of a table row for this lane: one Frag, or -- the wide fp8 kernel -- 8 fp8 values in
 // one 8-byte load.
@@ -610,11 +601,11 @@ __device__ inline void opt_step(const OptParams& o, float g, float& p, float& s0
 }
 
 // The same step for a table of dtype TV: fp8 tables on the hardware square root / reciprocal
-// (FM_FP8_FAST_EPI, above).  Every writer of a table row (in-place backward, owner apply, dense
+// (the cheaper epilogue above).  Every writer of a table row (in-place backward, owner apply, dense
 // apply) goes through this, so a row gets the same bits whichever path updates it.
 template <typename TV>
 __device__ inline void opt_step_tv(const OptParams& o, float g, float& p, float& s0, float& s1) {
-  if constexpr (FM_FP8_FAST_EPI && StateBf16<TV>::v) {
+  if constexpr (StateBf16<TV>::v) {
     if (o.type == kOptFtrl) {
       const float ilr = __builtin_amdgcn_rcpf(o.lr);  // (wave-uniform: hoisted by the compiler)
       const float n_new = __builtin_fmaf(g, g, s0);

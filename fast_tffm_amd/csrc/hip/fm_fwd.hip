@@ -57,12 +57,6 @@ __device__ inline int seg_lookup(const FwdArgs& a, int k) {
   return s;
 }
 
-#ifndef FM_FWD_PREFETCH
-#define FM_FWD_PREFETCH 1
-#endif
-#ifndef FM_FWD_SPECIALIZE  // 0: every step runs the general (sharded) forward (A/B build variant "fwdgen")
-#define FM_FWD_SPECIALIZE 1
-#endif
 constexpr int kSelfBit = (int)0x80000000u;   // row index tag: this rank's own table row (SelfRows)
 // Rows of one example kept in flight per lane group: enough to cover a
 // Criteo-shaped example (39 features) in one round for K=64 (G=4 -> 10 row
@@ -88,63 +82,42 @@ constexpr int fwd_min_waves() {
 // 4 at 5 / 6 at 4 lose (profiles/r4/fwd_occupancy_ab.txt).  Latency-bound gathers: more waves hide
 // more than more loads per wave.  (A variant of the register accumulation needed 136 VGPRs
 // uncapped -- 3 waves -- and the 4-wave floor then bought 0.674 -> 0.643 ms: specialize_ab.txt.)
-#ifndef FM_FWD_LOCAL_W16
-#define FM_FWD_LOCAL_W16 7
-#endif
-#ifndef FM_FWD_UNR16
-#define FM_FWD_UNR16 2
-#endif
+constexpr int kFwdWaves16 = 7;
+constexpr int kFwdUnr16 = 2;
 // The same pair for the 32-lane instantiations (k = 128): fp8 rows 4 at 7 waves (72 VGPRs):
 // k128 fp8 FTRL 0.806 -> 0.784 ms; bf16 / fp32 rows keep 12 at 4 (lower pairs spill there: k128
-// bf16 FTRL 0.95 -> 1.07-1.21 ms; profiles/r4/fwd_occupancy_ab.txt).  FM_FWD_UNR32[_FP8] /
-// FM_FWD_LOCAL_W32[_FP8]: A/B knobs.
-#ifndef FM_FWD_LOCAL_W32
-#define FM_FWD_LOCAL_W32 4
-#endif
-#ifndef FM_FWD_UNR32
-#define FM_FWD_UNR32 12
-#endif
-#ifndef FM_FWD_LOCAL_W32_FP8
-#define FM_FWD_LOCAL_W32_FP8 7
-#endif
-#ifndef FM_FWD_UNR32_FP8
-#define FM_FWD_UNR32_FP8 4
-#endif
+// bf16 FTRL 0.95 -> 1.07-1.21 ms; profiles/r4/fwd_occupancy_ab.txt).
+constexpr int kFwdWaves32 = 4;
+constexpr int kFwdUnr32 = 12;
+constexpr int kFwdWaves32Fp8 = 7;
+constexpr int kFwdUnr32Fp8 = 4;
 // The 4-lane bf16 instantiation (k = 16 bf16): 5 row groups in flight at >= 4 waves per SIMD instead
 // of 3 at the compiler's choice: k16 bf16 0.490-0.491 -> 0.485-0.488 ms over four same-box reps; 8 waves
 // lose 4-36%, 6 at 4 / 8 at 3 / 4 at 5 tie or lose (profiles/r4/fwd_occupancy_ab.txt).  Other dtypes
-// of 4-lane rows keep the generic choice.  FM_FWD_LOCAL_W4 / FM_FWD_UNR4: A/B knobs (0 = generic).
-#ifndef FM_FWD_LOCAL_W4
-#define FM_FWD_LOCAL_W4 4
-#endif
-#ifndef FM_FWD_UNR4
-#define FM_FWD_UNR4 5
-#endif
+// of 4-lane rows keep the generic choice (FwdUnroll, fwd_min_waves).
+constexpr int kFwdWaves4Bf16 = 4;
+constexpr int kFwdUnr4Bf16 = 5;
 // The sharded forward's 16-lane rows (k = 64): its row address takes two broadcasts and a 64-bit
 // add (the local kernel's: one broadcast and a mad), a longer per-row-group chain, and 2 row groups
 // at 7 waves ran 0.70 ms EMIT (fwd 228-244 us vs the local kernel's 175): 10 in flight at 4 waves
-// instead (FM_FWD_UNR16_SH / FM_FWD_SH_W16, A/B build variants).
-#ifndef FM_FWD_UNR16_SH
-#define FM_FWD_UNR16_SH 10
-#endif
-#ifndef FM_FWD_SH_W16
-#define FM_FWD_SH_W16 4
-#endif
+// instead (the row groups x waves table of profiles/r5/emit_ab.txt).
+constexpr int kFwdWaves16Sh = 4;
+constexpr int kFwdUnr16Sh = 10;
 template <typename TV>
 constexpr bool fwd_is_bf16() { return std::is_same<TV, __hip_bfloat16>::value; }
 template <int LPR, typename TV, bool SH = false>
 constexpr int fwd_local_min_waves() {
-  return LPR == 4 && fwd_is_bf16<TV>() && FM_FWD_LOCAL_W4 > 0 ? FM_FWD_LOCAL_W4
-         : LPR == 16 ? (SH && !Frag<TV>::kScaled ? FM_FWD_SH_W16 : FM_FWD_LOCAL_W16)
-         : LPR == 32 ? (Frag<TV>::kScaled ? FM_FWD_LOCAL_W32_FP8 : FM_FWD_LOCAL_W32)
+  return LPR == 4 && fwd_is_bf16<TV>() ? kFwdWaves4Bf16
+         : LPR == 16 ? (SH && !Frag<TV>::kScaled ? kFwdWaves16Sh : kFwdWaves16)
+         : LPR == 32 ? (Frag<TV>::kScaled ? kFwdWaves32Fp8 : kFwdWaves32)
                      : fwd_min_waves<LPR, TV>();
 }
 template <int LPR, typename TV, bool SH = false>
 constexpr int fwd_unroll() {
-  return LPR == 16 && SH && !Frag<TV>::kScaled ? FM_FWD_UNR16_SH
-         : LPR == 4 && fwd_is_bf16<TV>() && FM_FWD_UNR4 > 0 ? FM_FWD_UNR4
-         : LPR == 16 ? FM_FWD_UNR16
-         : LPR == 32 ? (Frag<TV>::kScaled ? FM_FWD_UNR32_FP8 : FM_FWD_UNR32)
+  return LPR == 16 && SH && !Frag<TV>::kScaled ? kFwdUnr16Sh
+         : LPR == 4 && fwd_is_bf16<TV>() ? kFwdUnr4Bf16
+         : LPR == 16 ? kFwdUnr16
+         : LPR == 32 ? (Frag<TV>::kScaled ? kFwdUnr32Fp8 : kFwdUnr32)
                      : FwdUnroll<kWave / LPR>::v;
 }
 
@@ -247,7 +220,6 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
   // pairs one example ahead, so while example i's rows are in flight the next example's pairs
   // are too, and example i starts with its pairs already in registers: one latency per example.
   // (Longer examples load their further 64-wide pieces in place.)
-  constexpr bool kPrefetch = FM_FWD_PREFETCH;  // (A/B build variant "fwdnopf": 0)
   auto pairs = [&](int base, int m, int& row, float& x) {
     row = 0;
     x = 0.f;
@@ -283,7 +255,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
   if (wave < a.B) {
     s = a.offsets[wave];
     e = a.offsets[wave + 1];
-    if (kPrefetch) pairs(s, min(kWave, e - s), p_row, p_x);
+    pairs(s, min(kWave, e - s), p_row, p_x);
   }
   if (wave + nwaves < a.B) {
     sn = a.offsets[wave + nwaves];
@@ -293,7 +265,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
     // next example's first pairs (its offsets arrived an example ago), the offsets after it
     int n_row = 0;
     float n_x = 0.f;
-    if (kPrefetch) pairs(sn, i + nwaves < a.B ? min(kWave, en - sn) : 0, n_row, n_x);
+    pairs(sn, i + nwaves < a.B ? min(kWave, en - sn) : 0, n_row, n_x);
     int snn = 0, enn = 0;
     if (i + 2 * nwaves < a.B) {
       snn = a.offsets[i + 2 * nwaves];
@@ -301,7 +273,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
     }
     // label / weight of example i: needed after the reduction, loaded now
     float y_pre = 0.f, wt_pre = 1.f;
-    if (!kPark && kPrefetch && a.loss_type != kLossNone && lane == 0) {
+    if (!kPark && a.loss_type != kLossNone && lane == 0) {
       y_pre = a.labels[i];
       if (a.weights) wt_pre = a.weights[i];
     }
@@ -315,7 +287,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
       int my_row = 0;
       float my_x = 0.f, my_w = 0.f, my_s = 1.f, my_n2 = 0.f;
       uint32_t my_t = 0;  // (SH) the occurrence's row in its source, bit 31: an own (table) row
-      if (kPrefetch && base == s) {
+      if (base == s) {
         my_row = p_row;
         my_x = p_x;
       } else {
@@ -459,9 +431,7 @@ __device__ __forceinline__ void fwd_body(const FwdArgs& a) {
     } else {
       float l = 0.f, d = 0.f;
       if (a.loss_type != kLossNone && lane == 0) {
-        const float y = kPrefetch ? y_pre : a.labels[i];
-        const float wt = kPrefetch ? wt_pre : (a.weights ? a.weights[i] : 1.f);
-        fwd_loss(a.loss_type, pred, y, wt, l, d);
+        fwd_loss(a.loss_type, pred, y_pre, wt_pre, l, d);
       }
       if (lane == 0) {
         a.pred[i] = pred;
@@ -598,7 +568,7 @@ int launch_fwd(const FwdArgs& a, int dtype, int grid, hipStream_t st) {
 
   // all-ones x (fp32 rows, fwd_nox): no broadcast of x, no multiply by it
   const bool nox = a.vals == nullptr && dtype == kF32;
-  if (a.self.u1 > a.self.u0 || a.seg_idx || !FM_FWD_SPECIALIZE || !table_rows) {
+  if (a.self.u1 > a.self.u0 || a.seg_idx || !table_rows) {
     if (nox) { FM_DISPATCH_LPR(lpr, fm_fwd_shard_kernel_nox, float, grid, 0, st, a); }
     else { FM_DISPATCH(dtype, lpr, fm_fwd_shard_kernel, grid, st, a); }
   } else {

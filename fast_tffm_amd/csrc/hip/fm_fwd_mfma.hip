@@ -52,26 +52,6 @@ static_assert(kMfMaxRows % 64 == 0, "row passes cover whole 64-row groups");
 
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 
-// FM_MF_PROF=1 (build variant "mfprof"): per-phase shader-clock totals of the kernel's waves
-// (tile start -> indices -> tails -> row pass -> K-loop -> epilogue; [5] = tiles), read and
-// cleared by the module's mf_prof()
-#ifndef FM_MF_PROF
-#define FM_MF_PROF 0
-#endif
-#if FM_MF_PROF
-__device__ unsigned long long g_mf_prof[8];
-#define MF_T(i)                                                                         \
-  do {                                                                                  \
-    const long long t_ = clock64();                                                     \
-    if (lane == 0) atomicAdd(&g_mf_prof[i], (unsigned long long)(t_ - t_last));        \
-    t_last = t_;                                                                        \
-  } while (0)
-#else
-#define MF_T(i) \
-  do {          \
-  } while (0)
-#endif
-
 // global_load_lds in inline asm (LDS destination: M0 = the wave-uniform LDS byte address, + 16 B x lane):
 // the compiler does not track these, so it inserts no vmcnt waits of its own for the LDS they write (with
 // the builtin it drains vmcnt to 0 before every LDS read of the same array, which serialises the ring);
@@ -109,10 +89,6 @@ __global__ __launch_bounds__(kBlock) void fm_fwd_mfma_fp8_kernel(FwdArgs a) {
   float loss_acc = 0.f, regv_acc = 0.f, regw_acc = 0.f;
   const int ntile = (a.B + kMfT - 1) / kMfT;
   for (int tile = blockIdx.x * kWavesPerBlock + wv; tile < ntile; tile += gridDim.x * kWavesPerBlock) {
-#if FM_MF_PROF
-    long long t_last = clock64();
-    if (lane == 0) atomicAdd(&g_mf_prof[5], 1ull);
-#endif
     const int e0 = tile * kMfT;
     const int ne = min(kMfT, a.B - e0);
     // tile-relative CSR offsets of its examples: lane m <= ne holds offsets[e0 + m] (lanes past ne: the end)
@@ -139,13 +115,11 @@ __global__ __launch_bounds__(kBlock) void fm_fwd_mfma_fp8_kernel(FwdArgs a) {
     // 1. row indices, then the rows' tails, into LDS
     for (int p = 0; p < nI; ++p) mf_glds4(a.rows + R0 + min(p * kWave + lane, R - 1), W + kMfOffIdx + p * 256);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    MF_T(0);
     for (int p = 0; p < nI; ++p) {
       const int id = idx_l[min(p * kWave + lane, R - 1)];
       mf_glds16(a.w + (uint64_t)(uint32_t)id * 4u, W + p * 1024);
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    MF_T(1);
     // 2. per row: example, lin / s2n sums, scale exponent
     int maxE = 0;
     for (int p = 0; p < nI; ++p) {
@@ -180,7 +154,6 @@ __global__ __launch_bounds__(kBlock) void fm_fwd_mfma_fp8_kernel(FwdArgs a) {
       const int be = E - maxE + 29;
       xs_l[r] = E == 0 ? 0 : be >= 1 ? (uint8_t)(be << 2) : be == 0 ? 2 : be == -1 ? 1 : 0;
     }
-    MF_T(2);
     // 3. K-steps
     const int S = (R + kMfKS - 1) / kMfKS;
     mf_v4f acc[8];
@@ -221,7 +194,6 @@ __global__ __launch_bounds__(kBlock) void fm_fwd_mfma_fp8_kernel(FwdArgs a) {
         acc[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf8_fp8(afrag, __builtin_bit_cast(long, b), acc[t], 0, 0, 0);
       }
     }
-    MF_T(3);
     // 4. epilogue: lane (g, li) holds S1[4 g + i][16 t + li] * 2^c
     const float unscale = __uint_as_float((uint32_t)max(1, maxE - 14) << 23);  // 2^(maxE - 141)
     float sq[4] = {0.f, 0.f, 0.f, 0.f};
@@ -269,7 +241,6 @@ __global__ __launch_bounds__(kBlock) void fm_fwd_mfma_fp8_kernel(FwdArgs a) {
         if (a.dpred) a.dpred[e0 + lane] = d * a.grad_scale;
       }
     }
-    MF_T(4);
   }
   if (a.loss_partial == nullptr && a.reg_partial == nullptr) return;
   loss_acc = group_sum<kWave>(loss_acc);

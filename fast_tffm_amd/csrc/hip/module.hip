@@ -88,16 +88,6 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
   m.def("fwd_grid", &fm::fwd_grid, py::arg("B"));
   m.def("fwd_mfma_enabled", &fm::fwd_mfma_enabled);
   m.def("set_fwd_mfma", &fm::set_fwd_mfma, py::arg("on"));
-#if FM_MF_PROF
-  m.def("mf_prof", [] {  // (build variant "mfprof") phase clocks of the MFMA forward, then cleared
-    unsigned long long h[8] = {};
-    hipDeviceSynchronize();
-    hipMemcpyFromSymbol(h, HIP_SYMBOL(fm::g_mf_prof), sizeof(h));
-    const unsigned long long z[8] = {};
-    hipMemcpyToSymbol(HIP_SYMBOL(fm::g_mf_prof), z, sizeof(z));
-    return std::vector<unsigned long long>(h, h + 8);
-  });
-#endif
   m.def("lanes_per_row", &fm::lanes_per_row, py::arg("Kp"), py::arg("dtype"));
 
   m.def(
@@ -264,6 +254,7 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
   m.def("radix_sort_ws_bytes", &fm::radix_sort_ws_bytes, py::arg("n"));
   m.def("bwd_wide_launches", &fm::bwd_wide_launches);  // launches of the wide fp8 chunk kernel so far
+  m.def("set_fp8_wide", &fm::set_fp8_wide, py::arg("on"));  // test hook: false = the 4-value fp8 kernels
   m.def("set_sort_spin_cap", &fm::set_sort_spin_cap, py::arg("cap"));  // (< 0: injected look-back failure)
   m.def(
       "device_errors",  // the current device's sticky error word (synchronous), cleared when `clear`

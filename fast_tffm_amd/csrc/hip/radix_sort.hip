@@ -90,10 +90,7 @@ constexpr int kOsSpinCap = 1 << 20;
 // the error without waiting -- the tests' fault injection)
 static int g_os_spin_cap = kOsSpinCap;
 void set_sort_spin_cap(int cap) { g_os_spin_cap = cap; }
-#ifndef FM_OS_LOOKBACK
-#define FM_OS_LOOKBACK 4
-#endif
-constexpr int kOsLookback = FM_OS_LOOKBACK;  // predecessor tiles read per look-back round
+constexpr int kOsLookback = 4;  // predecessor tiles read per look-back round
 
 // Fused producers of the sort's input (the dedup chain's two map kernels folded into the sort):
 // keys from row ids under the sharded-key map, written by the histogram kernel, and the payload

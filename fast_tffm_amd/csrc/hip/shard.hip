@@ -571,19 +571,14 @@ int launch_apply_runs(const ApplyArgs& a, int* match, int dtype, hipStream_t st)
                        a.run_off, a.req, match);
   }
   const int lpr = lanes_per_row(a.Kp, dtype);
-#ifndef FM_FP8_WIDE_APPLY
-#define FM_FP8_WIDE_APPLY FM_FP8_WIDE  // (the owner apply alone: the "fp8narrowapply" variant, A/B)
-#endif
-#if FM_FP8_WIDE_APPLY
   // wide fp8 rows (k = 128: 16 lanes x 8 values; rows, state and gradient rows 8 / 16-byte aligned)
-  if (dtype == kFP8 && lpr == 32 && a.Kp % 8 == 0 && a.v_stride % 8 == 0 && a.s_stride % 8 == 0 && a.g_stride % 4 == 0 &&
-      (uintptr_t)a.v % 8 == 0 && (uintptr_t)a.s0v % 16 == 0 && (uintptr_t)a.s1v % 16 == 0 &&
+  if (g_fp8_wide && dtype == kFP8 && lpr == 32 && a.Kp % 8 == 0 && a.v_stride % 8 == 0 && a.s_stride % 8 == 0 &&
+      a.g_stride % 4 == 0 && (uintptr_t)a.v % 8 == 0 && (uintptr_t)a.s0v % 16 == 0 && (uintptr_t)a.s1v % 16 == 0 &&
       (uintptr_t)a.grad_in % 16 == 0) {
     const int grid = fill_grid(a.R, kWavesPerBlock * (kWave / 16));
     hipLaunchKernelGGL((apply_runs_kernel<16, fp8e4m3, 8>), dim3(grid), dim3(kBlock), 0, st, a);
     return (int)hipGetLastError();
   }
-#endif
   const int grid = fill_grid(a.R, kWavesPerBlock * (kWave / lpr));
   FM_DISPATCH(dtype, lpr, apply_runs_kernel, grid, st, a);
   return (int)hipGetLastError();

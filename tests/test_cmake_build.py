@@ -21,3 +21,21 @@ def test_cmake_stamps_build_native_hashes(tmp_path):
     ninja = (tmp_path / "build.ninja").read_text()
     assert f'FM_BUILD_HASH=\\"{bn.cpu_hash()}\\"' in ninja
     assert f'FM_BUILD_HASH=\\"{bn.hip_hash()}\\"' in ninja
+
+
+def test_build_variants_name_live_switches():
+    """Every variant the driver builds for the suite exists, and every -DNAME= of a variant names a
+    macro the HIP sources still read (a stale flag would build a second copy of the default module)."""
+    import glob
+    import re
+
+    import __graft_entry__ as entry
+
+    assert set(entry.TEST_VARIANTS) <= set(bn.HIP_VARIANTS)
+    hip = os.path.join(bn.CSRC, "hip")
+    text = "".join(open(f).read() for f in sorted(glob.glob(os.path.join(hip, "*"))))
+    for name, flags in bn.HIP_VARIANTS.items():
+        for flag in flags:
+            m = re.fullmatch(r"-D(\w+)=.*", flag)
+            assert m, (name, flag)
+            assert re.search(rf"\b{m.group(1)}\b", text), (name, flag)

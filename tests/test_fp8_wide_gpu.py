@@ -1,9 +1,10 @@
-"""The wide fp8 chunk backward (hip/fm_bwd.hip, FM_FP8_WIDE: k=128 fp8 rows reduced with 8 values per
-lane, 16-byte r1 / state accesses) against the 4-value kernel it replaces, built as the "fp8narrow"
-variant: local training steps must leave every byte of the table -- fp8 rows, [w, scale, norm] rows,
-bf16 optimizer state -- identical (same per-element arithmetic, stochastic-rounding columns and norm
-butterfly: fm_common.h store_row_fp8x8).  Adagrad and FTRL, with and without feature values, batches
-with single-occurrence rows (short block), mid-length chunks and hot rows (partials + combines).
+"""The wide fp8 chunk backward (hip/fm_bwd.hip: k=128 fp8 rows reduced with 8 values per lane, 16-byte
+r1 / state accesses) against the 4-value kernel it replaces, which the same module runs under
+set_fp8_wide(False) (the launchers' fallback, forced): local training steps must leave every byte of
+the table -- fp8 rows, [w, scale, norm] rows, bf16 optimizer state -- identical (same per-element
+arithmetic, stochastic-rounding columns and norm butterfly: fm_common.h store_row_fp8x8).  Adagrad and
+FTRL, with and without feature values, batches with single-occurrence rows (short block), mid-length
+chunks and hot rows (partials + combines).
 """
 
 import os
@@ -34,6 +35,21 @@ def _batches(with_vals: bool):
     return out
 
 
+def _train_narrow(*args):
+    """_train on the 4-value kernels: the wide launches counter must not move."""
+    from fast_tffm_amd.ops import native
+
+    h = native.hip()
+    was = h.set_fp8_wide(False)
+    try:
+        n0 = h.bwd_wide_launches()
+        out = _train(*args)
+        assert h.bwd_wide_launches() == n0
+    finally:
+        h.set_fp8_wide(was)
+    return out
+
+
 def _train(opt: str, batches, dist=None, split="auto"):
     o = K.OptConfig("ftrl", lr=0.05, l1=0.01, l2=0.01, beta=1.0) if opt == "ftrl" else K.OptConfig("adagrad", lr=0.05)
     cfg = FMConfig(vocabulary_size=V, factor_num=128, loss_type="logistic", batch_size=B, init_value_range=0.05, seed=3,
@@ -59,13 +75,7 @@ def test_wide_fp8_backward_is_bitwise_the_narrow_one(opt, with_vals, monkeypatch
     n0 = native.hip().bwd_wide_launches()
     wide = _train(opt, batches)
     assert native.hip().bwd_wide_launches() - n0 == STEPS  # (the wide kernel ran every step)
-    monkeypatch.setenv("FM_HIP_VARIANT", "fp8narrow")
-    try:
-        native.hip()
-    except native.NativeExtensionError as e:
-        pytest.skip(f"fp8narrow build variant not available: {e}")
-    narrow = _train(opt, batches)
-    assert native.hip().bwd_wide_launches() == 0
+    narrow = _train_narrow(opt, batches)
     assert len(wide) == len(narrow)
     names = ["v", "wx", "s0v", "s0w", "s1v", "s1w"][: len(wide)]
     bad = {}
@@ -106,11 +116,6 @@ def test_wide_fp8_emit_backward_is_bitwise_the_narrow_one(rccl_ctx, self_rows, s
     n0 = native.hip().bwd_wide_launches()
     wide = _train("ftrl", batches, rccl_ctx, split)
     assert native.hip().bwd_wide_launches() > n0
-    monkeypatch.setenv("FM_HIP_VARIANT", "fp8narrow")
-    try:
-        native.hip()
-    except native.NativeExtensionError as e:
-        pytest.skip(f"fp8narrow build variant not available: {e}")
-    narrow = _train("ftrl", batches, rccl_ctx, split)
+    narrow = _train_narrow("ftrl", batches, rccl_ctx, split)
     for n, a, b in zip(["v", "wx", "s0v", "s0w", "s1v", "s1w"], wide, narrow):
         assert torch.equal(a.view(torch.uint8), b.view(torch.uint8)), n

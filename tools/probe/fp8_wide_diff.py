@@ -9,6 +9,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.dirname(os.path.abspa
 from fast_tffm_amd.data.synthetic import CriteoSynth  # noqa: E402
 from fast_tffm_amd.models.fm import FactorizationMachine, FMConfig  # noqa: E402
 from fast_tffm_amd.ops import kernels as K  # noqa: E402
+from fast_tffm_amd.ops import native  # noqa: E402
 
 V, B = 60_000, 8192
 gen = CriteoSynth(V, seed=13, device="cuda")
@@ -16,11 +17,15 @@ b = gen.batch(B)
 cnt = torch.bincount(b.ids.long(), minlength=V)
 
 
-def run(var, sr):
-    if var:
-        os.environ["FM_HIP_VARIANT"] = var
-    else:
-        os.environ.pop("FM_HIP_VARIANT", None)
+def run(wide, sr):
+    was = native.hip().set_fp8_wide(wide)
+    try:
+        return _run(sr)
+    finally:
+        native.hip().set_fp8_wide(was)
+
+
+def _run(sr):
     o = K.OptConfig("ftrl", lr=0.05, l1=0.01, l2=0.01, beta=1.0)
     cfg = FMConfig(vocabulary_size=V, factor_num=128, loss_type="logistic", batch_size=B, init_value_range=0.05,
                    seed=3, opt=o, dtype=K.FP8, factor_lambda=0.001, bias_lambda=0.001, stochastic_rounding=sr)
@@ -33,9 +38,8 @@ def run(var, sr):
     return out
 
 
-for sr, va, vb in ((False, None, None), (False, "fp8narrow", "fp8narrow"), (True, None, "fp8narrow"),
-                   (False, None, "fp8narrow")):
-    print(f"== {va} vs {vb}")
+for sr, va, vb in ((False, True, True), (False, False, False), (True, True, False), (False, True, False)):
+    print(f"== wide={va} vs wide={vb}")
     a, n = run(va, sr), run(vb, sr)
     for name, x, y in zip(("v", "s0v", "s1v"), a, n):
         bits = torch.uint8 if x.dtype == K.FP8 else torch.int16
