@@ -32,6 +32,7 @@ from ..data.batch import Batch
 from ..ops import kernels as K
 from ..utils.trace import roctx_range
 
+from .step import StepOut  # noqa: F401 -- (fast_tffm_amd.models.fm.StepOut: tests and tools import it here)
 from .table import FMTable, bits_for, rows_per_shard
 
 
@@ -76,15 +77,6 @@ class FMConfig:
     threads: int = 0                  # CPU kernels (0 = OpenMP default)
     global_bias: bool = False         # learned global bias b0 (extension; the reference has none)
     stochastic_rounding: bool = True  # bf16 / fp8 tables (GPU): stochastically rounded row stores
-
-
-@dataclass
-class StepOut:
-    loss_sum: torch.Tensor            # 0-d, summed weighted loss of this rank's batch
-    n: int                            # examples in this rank's batch
-
-    def mean_loss(self) -> float:
-        return float(self.loss_sum) / max(self.n, 1)
 
 
 class _Workspace:
@@ -485,7 +477,7 @@ class FactorizationMachine:
         The two branches only share read-only inputs; the join is an event, so
         the step stays asynchronous (and graph-capturable).
         """
-        ws, cfg = self.ws, self.cfg
+        ws = self.ws
         rows = self._rows32(b)
         gpu = self.device.type == "cuda"
         if gpu:
@@ -499,20 +491,38 @@ class FactorizationMachine:
         else:
             ex = K.csr_rows(b.offsets, out=ws.dd.ex_of_occ[: b.nnz], nnz=b.nnz)
         with roctx_range("fwd"):
-            fo = K.fm_forward(b.offsets, rows, b.vals, self.table.v, self.table.w, self.Kp, labels=b.labels,
-                              weights=b.weights, loss=cfg.loss_type, grad_scale=self.grad_scale(b.B), want_r1=True,
-                              pred=ws.pred[: b.B], r1=ws.r1[: b.B], dpred=ws.dpred[: b.B], partial=ws.fwd_partial,
-                              threads=cfg.threads, bias=self.gbias, defer_loss=gpu, max_feats=b.max_feats)
+            fo = self._train_forward(b, rows, self.table.v, self.table.w, total_B=b.B, defer_loss=gpu,
+                                     max_feats=b.max_feats)
             self.bias_step(fo.dpred)
         if gpu:
             main.wait_stream(side)
         else:
             dd = K.dedup(rows, ws=ws.dd, key_bits=bits_for(self.table.rows), ex_of_occ=ex, vals=b.vals)
+        self._local_backward(dd, fo)
+        return StepOut(fo.finish_loss(), b.B)
+
+    def _train_forward(self, sb: Batch, rows: torch.Tensor, src_v: torch.Tensor, src_w: torch.Tensor, *,
+                       total_B: int, e0: int = 0, **extra) -> K.FwdOut:
+        """The training forward of every executor: scores, loss and dL/dpred of the examples of ``sb`` (a
+        batch, or the part of one that starts at example ``e0``) over the rows ``src_v`` / ``src_w`` (the
+        table, or gathered wire rows), written into the workspace's ``pred`` / ``r1`` / ``dpred`` at
+        ``e0 : e0 + sb.B``.  ``rows``: each occurrence's row in the source.  ``total_B``: the examples of
+        the whole batch (the gradient's 1 / B).  ``extra``: what differs between the executors
+        (``defer_loss``, ``max_feats``, ``self_rows``, ``seg_lookup``), passed on to ``K.fm_forward``."""
+        ws, cfg = self.ws, self.cfg
+        e1 = e0 + sb.B
+        return K.fm_forward(sb.offsets, rows, sb.vals, src_v, src_w, self.Kp, labels=sb.labels, weights=sb.weights,
+                            loss=cfg.loss_type, grad_scale=self.grad_scale(total_B), want_r1=True,
+                            pred=ws.pred[e0:e1], r1=ws.r1[e0:e1], dpred=ws.dpred[e0:e1], partial=ws.fwd_partial,
+                            threads=cfg.threads, bias=self.gbias, **extra)
+
+    def _local_backward(self, dd, fo: K.FwdOut) -> None:
+        """Backward fused with the optimizer's in-place update of the touched table rows (dedup ``dd`` ready)."""
+        ws, cfg = self.ws, self.cfg
         rv, rw = self.reg_coeffs
         with roctx_range("bwd+update"):
             K.fm_backward(dd, fo.dpred, fo.r1, self.Kp, mode=K.BWD_LOCAL, table=self.table.state, opt=cfg.opt,
                           reg_v=rv, reg_w=rw, partial=ws.bwd_partial, threads=cfg.threads, sr_counter=self.sr_tick())
-        return StepOut(fo.finish_loss(), b.B)
 
     # ------------------------------------------------------------------
     def _local_plan(self, b: Batch, inputs_ready=None, avoid: int | None = None) -> "_LocalPlan":
@@ -559,52 +569,61 @@ class FactorizationMachine:
 
     def _fwd_bwd_local(self, b: Batch, rows: torch.Tensor, dd) -> StepOut:
         """Forward + loss + backward/update of ``b`` on the current stream (dedup ``dd`` ready)."""
-        ws, cfg = self.ws, self.cfg
-        rv, rw = self.reg_coeffs
         with roctx_range("fwd"):
-            fo = K.fm_forward(b.offsets, rows, b.vals, self.table.v, self.table.w, self.Kp, labels=b.labels,
-                              weights=b.weights, loss=cfg.loss_type, grad_scale=self.grad_scale(b.B), want_r1=True,
-                              pred=ws.pred[: b.B], r1=ws.r1[: b.B], dpred=ws.dpred[: b.B], partial=ws.fwd_partial,
-                              threads=cfg.threads, bias=self.gbias, defer_loss=True, max_feats=b.max_feats)
+            fo = self._train_forward(b, rows, self.table.v, self.table.w, total_B=b.B, defer_loss=True,
+                                     max_feats=b.max_feats)
             self.bias_step(fo.dpred)
-        with roctx_range("bwd+update"):
-            K.fm_backward(dd, fo.dpred, fo.r1, self.Kp, mode=K.BWD_LOCAL, table=self.table.state, opt=cfg.opt,
-                          reg_v=rv, reg_w=rw, partial=ws.bwd_partial, threads=cfg.threads,
-                          sr_counter=self.sr_tick())
+        self._local_backward(dd, fo)
         return StepOut(fo.finish_loss(), b.B)
+
+    def _inputs_ready(self, batch: Batch | None):
+        """Event after everything enqueued on the current stream so far -- the producers of an upcoming
+        ``batch`` -- for its plan to wait on; None without a batch, or when it carries a ``ready`` event."""
+        if batch is None or getattr(batch, "ready", None) is not None:
+            return None
+        ev = torch.cuda.Event()
+        ev.record(torch.cuda.current_stream(self.device))
+        return ev
+
+    def _take_local_plan(self, b: Batch) -> "_LocalPlan":
+        """The plan of ``b``: the pending one when the previous step planned ``b`` ahead (the plan after
+        it moves up); otherwise the pending plans are for batches that are not coming, and ``b`` is
+        planned now."""
+        pl = self._lpending
+        if pl is not None and pl.b is b:
+            self._lpending, self._lpending2 = self._lpending2, None
+            return pl
+        self._lpending = self._lpending2 = None
+        return self._local_plan(b)
+
+    def _plan_ahead(self, next_batch: Batch | None, next2: Batch | None, nb_ready, avoid: int | None = None) -> None:
+        """Start the plans of the next batch and, with the depth-2 lookahead, of the one after it, unless
+        they are pending already.  ``nb_ready``: ``_inputs_ready(next_batch)`` taken at the start of the
+        step; ``next2`` gets an event of now when there is none.  ``avoid``: as for ``_local_plan``."""
+        if next_batch is not None and (self._lpending is None or self._lpending.b is not next_batch):
+            self._lpending = self._local_plan(next_batch, nb_ready, avoid=avoid)
+            self._lpending2 = None
+        if (next2 is not None and self._lpending is not None and self._lpending2 is None
+                and os.environ.get("FM_LOCAL_DEPTH2", "1") != "0"):  # (0: one batch of lookahead only)
+            if nb_ready is None:
+                nb_ready = self._inputs_ready(next2)
+            self._lpending2 = self._local_plan(next2, nb_ready, avoid=avoid)
 
     def _local_lookahead_step(self, b: Batch, next_batch: Batch | None, next2: Batch | None = None) -> StepOut:
         """Eager local step with lookahead: the dedup of ``next_batch`` runs on the side stream
         concurrently with this step's forward + backward (the dedup of ``b`` was done the same
         way during the previous step), taking the sort off the critical path.  With ``next2``
-        (depth-2 lookahead, FM_LOCAL_DEPTH2 != 0) the dedup of the batch after that is started
+        (depth-2 lookahead, ``_plan_ahead``) the dedup of the batch after that is started
         too, so a plan has a whole step of slack before its step needs it."""
-        ws, cfg = self.ws, self.cfg
         main = torch.cuda.current_stream(self.device)
-        nb_ready = None
-        if next_batch is not None and getattr(next_batch, "ready", None) is None:
-            nb_ready = torch.cuda.Event()   # next_batch's producers: everything enqueued so far
-            nb_ready.record(main)
-        pl = self._lpending
-        if pl is not None and pl.b is b:
-            self._lpending, self._lpending2 = self._lpending2, None
-        else:
-            self._lpending = self._lpending2 = None
-            pl = self._local_plan(b)
+        nb_ready = self._inputs_ready(next_batch)
+        pl = self._take_local_plan(b)
         main.wait_event(pl.ready)
         out = self._fwd_bwd_local(b, pl.rows, pl.dd)
         done = torch.cuda.Event()
         done.record(main)
         self._lslots[pl.slot].done = done
-        if next_batch is not None and (self._lpending is None or self._lpending.b is not next_batch):
-            self._lpending = self._local_plan(next_batch, nb_ready)
-            self._lpending2 = None
-        if (next2 is not None and self._lpending is not None and self._lpending2 is None
-                and os.environ.get("FM_LOCAL_DEPTH2", "1") != "0"):
-            if getattr(next2, "ready", None) is None and nb_ready is None:
-                nb_ready = torch.cuda.Event()
-                nb_ready.record(main)
-            self._lpending2 = self._local_plan(next2, nb_ready)
+        self._plan_ahead(next_batch, next2, nb_ready)
         return out
 
     def lookahead_graph_buffers(self, example: Batch, n: int = 4) -> list[Batch]:
@@ -653,8 +672,12 @@ class FactorizationMachine:
         ``FwdOut.r1`` (every example's ``sum_j x_j v_j``, a fresh tensor)."""
         if self.closed and self.mode != "local":
             raise RuntimeError("forward on a closed multi-rank FactorizationMachine")
-        if self._exchange is not None:
+        if self.mode == "shard":
             return self._exchange.forward(b, loss=loss, want_reg=want_reg, want_r1=want_r1)
+        return self._local_forward(b, loss=loss, want_reg=want_reg, want_r1=want_r1)
+
+    def _local_forward(self, b: Batch, *, loss: str, want_reg: bool, want_r1: bool) -> K.FwdOut:
+        """``forward`` on this rank's own table: the local model and the replicas of dp / dp_dense."""
         rows = b.ids.to(torch.int32)
         return K.fm_forward(b.offsets, rows, b.vals, self.table.v, self.table.w, self.Kp, labels=b.labels,
                             weights=b.weights, loss=loss, grad_scale=1.0, want_r1=want_r1, want_reg=want_reg,
@@ -671,8 +694,12 @@ class FactorizationMachine:
         Row-sharded models gather the batch's rows like ``forward`` (a collective: every rank calls)."""
         if self.closed and self.mode != "local":
             raise RuntimeError("explain on a closed multi-rank FactorizationMachine")
-        if self._exchange is not None:
+        if self.mode == "shard":
             return self._exchange.explain(b)
+        return self._local_explain(b)
+
+    def _local_explain(self, b: Batch) -> tuple[torch.Tensor, torch.Tensor]:
+        """``explain`` on this rank's own table (local, dp, dp_dense)."""
         return K.fm_explain(b.offsets, b.ids.to(torch.int32), b.vals, self.table.v, self.table.w, self.Kp,
                             bias=self.gbias, threads=self.cfg.threads)
 

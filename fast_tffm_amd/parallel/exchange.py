@@ -38,6 +38,7 @@ import torch.distributed as dist
 
 from ..data.batch import Batch
 from ..ops import kernels as K
+from ..models.step import StepOut
 from ..models.table import bits_for
 from ..utils.trace import roctx_range
 
@@ -675,16 +676,10 @@ class ShardExchange(_Base):
         previous step's gradient (apply stream), forward + backward on the exchanged rows only, gradient
         all-to-all (pending: applied during the next step), then the next plans and the next step's rows
         (gathered right behind the apply just enqueued)."""
-        from ..models.fm import StepOut
-
         m, ws, cfg, Kp = self.m, self.m.ws, self.m.cfg, self.Kp
         gpu = self.dev.type == "cuda"
         wf = self.wire
-        build = next2 if next2 is not None else next_batch
-        nb_ready = None
-        if build is not None and gpu and getattr(build, "ready", None) is None:
-            nb_ready = torch.cuda.Event()
-            nb_ready.record(self._main)
+        nb_ready = self._inputs_ready(next2 if next2 is not None else next_batch)
         with roctx_range("plan"):
             pl = self._take_plan(b, True)
         self.cur_plan = pl
@@ -712,15 +707,9 @@ class ShardExchange(_Base):
         sr = m.sr_tick()
         if sr is not None:
             sr = sr.clone()  # (this step's seed, read by its apply during the next step)
-        sb, dd = part.b, part.dd
-        with roctx_range("fwd"):
-            fo = K.fm_forward(sb.offsets, part.keys if part.seg is not None else dd.inv[: sb.nnz], sb.vals, src_v,
-                              src_w, Kp, labels=sb.labels, weights=sb.weights, loss=cfg.loss_type,
-                              grad_scale=m.grad_scale(b.B), want_r1=True, pred=ws.pred[: sb.B], r1=ws.r1[: sb.B],
-                              dpred=ws.dpred[: sb.B], partial=ws.fwd_partial, threads=cfg.threads, bias=m.gbias,
-                              seg_lookup=part.seg, defer_loss=True)
+        fo = self._forward_part(pl, part, src_v, src_w, b.B)
         with roctx_range("bwd"):
-            K.fm_backward(dd, fo.dpred, fo.r1, Kp, mode=K.BWD_EMIT, src_v=src_v, src_w=src_w,
+            K.fm_backward(part.dd, fo.dpred, fo.r1, Kp, mode=K.BWD_EMIT, src_v=src_v, src_w=src_w,
                           grad_out=grad_send[: max(pl.U, 1)], reg_v=rv, reg_w=rw, partial=ws.bwd_partial,
                           threads=cfg.threads, grad_bf16=wf.grad_bf16)
         m.bias_step(ws.dpred[: b.B])
@@ -736,22 +725,7 @@ class ShardExchange(_Base):
                 self.bytes_sent += 4 * wf.g_words * self._to_others(part.sc)
         self._pend = (pl, grad_recv, works, sr, bwd_ev)
         # the next plans; the next step's rows are gathered behind the apply enqueued above
-        if self.pending and next_batch is not None and self.pending[0].b is next_batch:
-            nxt_pl = self.pending[0]
-            with roctx_range("plan_finish_next"):
-                self._plan_finish(nxt_pl)
-            if nxt_pl.early is None and self._early_ok(nxt_pl, pl):
-                with roctx_range("early_rows_next"):
-                    self._early_ahead(nxt_pl, pl)
-        if next2 is not None and not any(p.b is next2 for p in self.pending):
-            if next_batch is not None and not any(p.b is next_batch for p in self.pending):
-                with roctx_range("plan_next"):
-                    self.pending.append(self._plan(next_batch, True, nb_ready, early=True))
-            with roctx_range("plan_next2"):
-                self.pending.append(self._plan_start(next2, True, nb_ready))
-        elif next2 is None and next_batch is not None and not any(p.b is next_batch for p in self.pending):
-            with roctx_range("plan_next"):
-                self.pending.append(self._plan(next_batch, True, nb_ready, early=True))
+        self._schedule_next(pl, next_batch, next2, nb_ready, True)
         return StepOut(loss, b.B)
 
     def _early_ahead(self, pl: _ShardPlan, cur: _ShardPlan) -> None:
@@ -1067,8 +1041,6 @@ class ShardExchange(_Base):
         of ``next2`` is built at the end of this step, and at the start of this step the early
         row exchange of the next batch (planned during the previous step) is launched, so the
         whole table-independent half of a step and its row exchange have a full step of slack."""
-        from ..models.fm import StepOut
-
         if self.dev.type == "cuda":
             self._main = torch.cuda.current_stream(self.dev)
         if self.staleness:
@@ -1079,11 +1051,7 @@ class ShardExchange(_Base):
             return self.m._local_train_step(b)
         m, ws, cfg, Kp = self.m, self.m.ws, self.m.cfg, self.Kp
         gpu = self.dev.type == "cuda"
-        build = next2 if next2 is not None else next_batch
-        nb_ready = None
-        if build is not None and gpu and getattr(build, "ready", None) is None:
-            nb_ready = torch.cuda.Event()  # the batch's producers: all work enqueued before this step
-            nb_ready.record(self._main)
+        nb_ready = self._inputs_ready(next2 if next2 is not None else next_batch)
         if gpu:
             self.step_start = torch.cuda.Event()  # after the previous step's apply (early gathers wait on it)
             self.step_start.record(self._main)
@@ -1105,7 +1073,6 @@ class ShardExchange(_Base):
         gworks = []
         loss = None
         rv, rw = m.reg_coeffs
-        gscale = m.grad_scale(b.B)
         # (one stochastic-rounding tick per step, shared by the in-place self-row updates of the
         # backward and the owner's apply: the same row gets the same bits either way)
         sr = m.sr_tick()
@@ -1117,18 +1084,12 @@ class ShardExchange(_Base):
         # one part: the loss reduction is enqueued after the backward, as in the local step
         one_part = len(pl.parts) == 1
         for part, (buf, work) in zip(pl.parts, rows):
-            sb, dd, e0 = part.b, part.dd, part.e0
+            dd = part.dd
             if work is not None:
                 work.wait()               # the compute stream waits for this part's rows
             src_v, src_w = wf.views(buf) if buf is not None else early_views
             gs = grad_send[part.u0: part.u0 + part.U]
-            with roctx_range("fwd"):
-                fo = K.fm_forward(sb.offsets, part.keys if part.seg is not None else dd.inv[: sb.nnz], sb.vals,
-                                  src_v, src_w, Kp, labels=sb.labels,
-                                  weights=sb.weights, loss=cfg.loss_type, grad_scale=gscale, want_r1=True,
-                                  pred=ws.pred[e0: e0 + sb.B], r1=ws.r1[e0: e0 + sb.B],
-                                  dpred=ws.dpred[e0: e0 + sb.B], partial=ws.fwd_partial, threads=cfg.threads,
-                                  bias=m.gbias, self_rows=srows, seg_lookup=part.seg, defer_loss=one_part)
+            fo = self._forward_part(pl, part, src_v, src_w, b.B, self_rows=srows)
             if not one_part:  # (the parts share the loss partials: each part's sum before the next)
                 loss = fo.loss_sum if loss is None else loss + fo.loss_sum
             if self._split_ok(pl, dd):
@@ -1156,10 +1117,43 @@ class ShardExchange(_Base):
                              ws=self.slots[pl.slot].ensure2(pl.R, self.dev) if not gpu else None,
                              grad_bf16=wf.grad_bf16, sr_counter=sr, self_run=self.ctx.rank if srows else -1,
                              self_excl=pl.self_excl)
-        if gpu:
-            done = torch.cuda.Event()
-            done.record(self._main)
-            self.slots[pl.slot].done = done
+        self._slot_done(self.slots[pl.slot])
+        self._schedule_next(pl, next_batch, next2, nb_ready, self.prefetch_depth1)
+        return StepOut(loss, b.B)
+
+    # ---- pieces shared by the synchronous step, the stale step and evaluation -----------------
+    def _inputs_ready(self, build: Batch | None):
+        """GPU: event after all work enqueued before this step, the producers of the batch ``build`` whose
+        plan the step will start (``FactorizationMachine._inputs_ready``); None on the CPU."""
+        return self.m._inputs_ready(build) if self.dev.type == "cuda" else None
+
+    @staticmethod
+    def _occ_rows(part: _Part) -> torch.Tensor:
+        """What the forward reads per occurrence of ``part``: its sharded key when the plan built a
+        bucket index (the segment lookup), otherwise its row in the gathered buffer (the inverse map)."""
+        return part.keys if part.seg is not None else part.dd.inv[: part.b.nnz]
+
+    def _forward_part(self, pl: _ShardPlan, part: _Part, src_v, src_w, total_B: int, **kw) -> K.FwdOut:
+        """Training forward of one part of ``pl`` over its exchanged rows (``_train_forward`` of the model).
+        A plan of one part defers the loss reduction behind the backward, as the local step does; several
+        parts share the loss partials, so each part's sum is taken before the next part's forward."""
+        with roctx_range("fwd"):
+            return self.m._train_forward(part.b, self._occ_rows(part), src_v, src_w, total_B=total_B, e0=part.e0,
+                                         seg_lookup=part.seg, defer_loss=len(pl.parts) == 1, **kw)
+
+    def _slot_done(self, slot: _PlanSlot) -> None:
+        """GPU: everything that reads ``slot``'s buffers is enqueued on the current stream; the slot's next
+        plan waits for it."""
+        if self.dev.type == "cuda":
+            slot.done = torch.cuda.Event()
+            slot.done.record(torch.cuda.current_stream(self.dev))
+
+    def _schedule_next(self, pl: _ShardPlan, next_batch: Batch | None, next2: Batch | None, nb_ready,
+                       full_depth1: bool) -> None:
+        """End of a step on plan ``pl``: finish the next batch's plan, launch its early row exchange and
+        start the plans of ``next_batch`` / ``next2`` that do not exist yet.  ``full_depth1``: with one
+        batch of lookahead, build the next plan in full now (with its early row exchange) instead of only
+        starting it (finished when the next step takes it)."""
         if self.pending and next_batch is not None and self.pending[0].b is next_batch:
             # Finish the next batch's plan only now, with this whole step already enqueued: the
             # host's wait for its owner counts (dedup on the plan stream, started one step ago)
@@ -1174,68 +1168,60 @@ class ShardExchange(_Base):
             if nxt_pl.early is None and self._early_ok(nxt_pl, pl):
                 with roctx_range("early_rows_next"):
                     self._early_ahead(nxt_pl, pl)
+        planned = next_batch is None or any(p.b is next_batch for p in self.pending)
         if next2 is not None and not any(p.b is next2 for p in self.pending):
-            if not any(p.b is next_batch for p in self.pending) and next_batch is not None:
+            if not planned:
                 with roctx_range("plan_next"):  # (first depth-2 step: the next batch has no plan yet)
                     self.pending.append(self._plan(next_batch, True, nb_ready, early=True))
             with roctx_range("plan_next2"):  # started now, finished at the start of the next step
                 self.pending.append(self._plan_start(next2, True, nb_ready))
-        elif next2 is None and next_batch is not None and not any(p.b is next_batch for p in self.pending):
+        elif next2 is None and not planned:
             with roctx_range("plan_next"):
-                if self.prefetch_depth1:  # built in full now, with its early row exchange
+                if full_depth1:  # built in full now, with its early row exchange
                     self.pending.append(self._plan(next_batch, True, nb_ready, early=True))
                 else:  # started now, finished when the next step takes it
                     self.pending.append(self._plan_start(next_batch, True, nb_ready))
-        return StepOut(loss, b.B)
 
-    @torch.no_grad()
-    def forward(self, b: Batch, *, loss: str = "none", want_reg: bool = False, want_r1: bool = False) -> K.FwdOut:
+    def _eval_rows(self, b: Batch):
+        """Opening of ``forward`` / ``explain``: an evaluation plan of ``b`` and the gather + exchange of its
+        rows from the table with every update applied; returns ``(pl, part, src_v, src_w)``."""
         self.flush()  # (staleness: evaluate the table with every update applied)
         self.m.ws.ensure(b.B, b.nnz)
         pl = self._take_plan(b, False)
         part = pl.parts[0]
-        buf, work = self._gather_part(pl, part, async_op=False)
-        src_v, src_w = self.wire.views(buf)
-        seg = getattr(part, "seg", None)  # (eval plans keep the inverse map: train=False)
-        out = K.fm_forward(b.offsets, part.keys if seg is not None else part.dd.inv[: b.nnz], b.vals, src_v, src_w,
-                           self.Kp, labels=b.labels, weights=b.weights, loss=loss, grad_scale=1.0, want_r1=want_r1,
-                           want_reg=want_reg, threads=self.m.cfg.threads, bias=self.m.gbias, seg_lookup=seg)
-        if self.dev.type == "cuda":
-            done = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(self.dev))
-            self.slots[pl.slot].done = done
+        buf, _ = self._gather_part(pl, part, async_op=False)
+        return (pl, part, *self.wire.views(buf))
+
+    @torch.no_grad()
+    def forward(self, b: Batch, *, loss: str = "none", want_reg: bool = False, want_r1: bool = False) -> K.FwdOut:
+        pl, part, src_v, src_w = self._eval_rows(b)
+        # (eval plans keep the inverse map, train=False: no segment lookup)
+        out = K.fm_forward(b.offsets, self._occ_rows(part), b.vals, src_v, src_w, self.Kp, labels=b.labels,
+                           weights=b.weights, loss=loss, grad_scale=1.0, want_r1=want_r1, want_reg=want_reg,
+                           threads=self.m.cfg.threads, bias=self.m.gbias, seg_lookup=part.seg)
+        self._slot_done(self.slots[pl.slot])
         return out
 
     @torch.no_grad()
     def explain(self, b: Batch) -> tuple[torch.Tensor, torch.Tensor]:
         """``forward``'s gather, then the attributions over the wire rows: the eval plan's inverse map is
         each occurrence's row in the gathered buffer (plain row indices, no segment lookup, no self rows)."""
-        self.flush()
-        self.m.ws.ensure(b.B, b.nnz)
-        pl = self._take_plan(b, False)
-        part = pl.parts[0]
-        buf, work = self._gather_part(pl, part, async_op=False)
-        src_v, src_w = self.wire.views(buf)
+        pl, part, src_v, src_w = self._eval_rows(b)
         out = K.fm_explain(b.offsets, part.dd.inv[: b.nnz], b.vals, src_v, src_w, self.Kp, bias=self.m.gbias,
                            threads=self.m.cfg.threads)
-        if self.dev.type == "cuda":
-            done = torch.cuda.Event()
-            done.record(torch.cuda.current_stream(self.dev))
-            self.slots[pl.slot].done = done
+        self._slot_done(self.slots[pl.slot])
         return out
 
 
 class DPExchange(_Base):
-    """Replicated table; sparse all-gather of (ids, gradient rows)."""
+    """Replicated table; sparse all-gather of (ids, gradient rows).  Evaluation (``forward``, ``explain``)
+    reads the replica: the model runs it itself."""
 
     def _local_grads(self, b: Batch):
         m, ws, cfg, Kp = self.m, self.m.ws, self.m.cfg, self.Kp
         rows = m._rows32(b)
         ex = K.csr_rows(b.offsets, out=ws.dd.ex_of_occ[: b.nnz], nnz=b.nnz)
-        fo = K.fm_forward(b.offsets, rows, b.vals, m.table.v, m.table.w, Kp, labels=b.labels, weights=b.weights,
-                          loss=cfg.loss_type, grad_scale=m.grad_scale(b.B), want_r1=True, pred=ws.pred[: b.B],
-                          r1=ws.r1[: b.B], dpred=ws.dpred[: b.B], partial=ws.fwd_partial, threads=cfg.threads,
-                          bias=m.gbias, max_feats=b.max_feats)
+        fo = m._train_forward(b, rows, m.table.v, m.table.w, total_B=b.B, max_feats=b.max_feats)
         m.bias_step(fo.dpred)
         dd = K.dedup(rows, ws=ws.dd, key_bits=bits_for(m.table.rows), ex_of_occ=ex, vals=b.vals,
                      num_examples=b.B, Kp=Kp)
@@ -1250,8 +1236,6 @@ class DPExchange(_Base):
         return fo, uniq, grad
 
     def train_step(self, b: Batch):
-        from ..models.fm import StepOut
-
         fo, uniq, grad = self._local_grads(b)
         U = uniq.numel()
         sizes_t = torch.tensor([U], dtype=torch.int64, device=self.dev)
@@ -1276,19 +1260,6 @@ class DPExchange(_Base):
         K.apply_rows(dd2, g_cat, self.m.table.state, self.m.cfg.opt, self.Kp, threads=self.m.cfg.threads,
                      sr_counter=self.m.sr_tick())
         return StepOut(fo.loss_sum, b.B)
-
-    @torch.no_grad()
-    def forward(self, b: Batch, *, loss: str = "none", want_reg: bool = False, want_r1: bool = False) -> K.FwdOut:
-        t = self.m.table
-        return K.fm_forward(b.offsets, b.ids.to(torch.int32), b.vals, t.v, t.w, self.Kp, labels=b.labels,
-                            weights=b.weights, loss=loss, grad_scale=1.0, want_r1=want_r1, want_reg=want_reg,
-                            threads=self.m.cfg.threads, bias=self.m.gbias, max_feats=b.max_feats)
-
-    @torch.no_grad()
-    def explain(self, b: Batch) -> tuple[torch.Tensor, torch.Tensor]:
-        t = self.m.table
-        return K.fm_explain(b.offsets, b.ids.to(torch.int32), b.vals, t.v, t.w, self.Kp, bias=self.m.gbias,
-                            threads=self.m.cfg.threads)
 
 
 def dp_dense_blocks(world: int) -> int:
@@ -1414,8 +1385,6 @@ class DPDenseExchange(DPExchange):
         return w
 
     def train_step(self, b: Batch, next_batch: Batch | None = None, next2: Batch | None = None):
-        from ..models.fm import StepOut
-
         if self.dev.type != "cuda":
             return self._train_step_reference(b)
         if self.local_w1:
@@ -1428,22 +1397,11 @@ class DPDenseExchange(DPExchange):
             return self.m._local_train_step(b)
         m, ws, cfg, Kp = self.m, self.m.ws, self.m.cfg, self.Kp
         main = torch.cuda.current_stream(self.dev)
-        nb_ready = None
-        if next_batch is not None and getattr(next_batch, "ready", None) is None:
-            nb_ready = torch.cuda.Event()
-            nb_ready.record(main)
-        pl = m._lpending
-        if pl is not None and pl.b is b:
-            m._lpending, m._lpending2 = m._lpending2, None
-        else:
-            m._lpending = m._lpending2 = None
-            pl = m._local_plan(b)
+        nb_ready = m._inputs_ready(next_batch)
+        pl = m._take_local_plan(b)
         main.wait_event(pl.ready)
         with roctx_range("fwd"):
-            fo = K.fm_forward(b.offsets, pl.rows, b.vals, m.table.v, m.table.w, Kp, labels=b.labels,
-                              weights=b.weights, loss=cfg.loss_type, grad_scale=m.grad_scale(b.B), want_r1=True,
-                              pred=ws.pred[: b.B], r1=ws.r1[: b.B], dpred=ws.dpred[: b.B], partial=ws.fwd_partial,
-                              bias=m.gbias, max_feats=b.max_feats)
+            fo = m._train_forward(b, pl.rows, m.table.v, m.table.w, total_B=b.B, max_feats=b.max_feats)
             m.bias_step(fo.dpred)
         rv, rw = m.reg_coeffs
         # backward pieces by key block, each block's reduce-scatter issued behind its piece
@@ -1463,15 +1421,7 @@ class DPDenseExchange(DPExchange):
         # like the local step -- the next step's forward / backward
         # (this step's slot has no done event yet -- the apply and zero_listed_rows below still read
         # its plan -- so the new plans avoid it)
-        if next_batch is not None and (m._lpending is None or m._lpending.b is not next_batch):
-            m._lpending = m._local_plan(next_batch, nb_ready, avoid=pl.slot)
-            m._lpending2 = None
-        if (next2 is not None and m._lpending is not None and m._lpending2 is None
-                and os.environ.get("FM_LOCAL_DEPTH2", "1") != "0"):
-            if getattr(next2, "ready", None) is None and nb_ready is None:
-                nb_ready = torch.cuda.Event()
-                nb_ready.record(main)
-            m._lpending2 = m._local_plan(next2, nb_ready, avoid=pl.slot)
+        m._plan_ahead(next_batch, next2, nb_ready, avoid=pl.slot)
         ag = []
         sr = m.sr_tick()
         with roctx_range("apply+all_gather"):
@@ -1495,8 +1445,6 @@ class DPDenseExchange(DPExchange):
         return StepOut(fo.loss_sum, b.B)
 
     def _train_step_reference(self, b: Batch):
-        from ..models.fm import StepOut
-
         fo, uniq, grad = self._local_grads(b)
         dense = self.dense
         dense.zero_()
