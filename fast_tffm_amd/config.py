@@ -31,10 +31,17 @@ Extensions (new keys, all optional):
                 validation_gauc = true|false (grouped AUC of the validation scores, printed and logged after the
                                 AUC / loss lines; needs validation_group_files; default false),
                 gauc_tolerance = <float> (stop when the validation GAUC is >= it; needs validation_gauc),
+                validation_ndcg = <K> (mean NDCG@K over the validation groups with a positive, printed and logged
+                                after the GAUC / AUC / loss lines; one integer in [1, 4096]; needs
+                                validation_group_files), ndcg_tolerance = <float> (stop when the validation
+                                NDCG@K is >= it; needs validation_ndcg),
                 checkpoint_format = dense|sparse (sparse: a checkpoint stores only the rows that differ from
                                 their counter-based init, and restore regenerates the others; default dense)
   [Predict]     predict_group_files = <files> (one group key per line, parallel to predict_files: the
-                                ``evaluate`` task then reports the grouped AUC and writes <file>_gauc)
+                                ``evaluate`` task then reports the grouped AUC and writes <file>_gauc),
+                rank_cutoffs = <K>[,<K>...] (1 to 4 ascending integers in [1, 4096]: ``evaluate`` then also
+                                reports NDCG@K, recall@K and precision@K per group and writes <file>_rank; needs
+                                predict_group_files)
   [Distributed] mode = auto|local|shard|dp|dp_dense, grad_reduce = sum|mean,
                 comm_dtype = auto|fp32|bf16 (row-sharded wire rows; auto = table storage dtype),
                 microbatches = 1|2|... (row-sharded step parts overlapping the exchange; default 1),
@@ -124,9 +131,12 @@ class FMRunConfig:
     validation_group_files: list[str] = field(default_factory=list)  # one group key per validation line
     validation_gauc: bool = False        # report the grouped AUC of the validation scores
     gauc_tolerance: float | None = None  # stop when the validation GAUC is >= this
+    validation_ndcg: int | None = None   # report the mean NDCG@K of the validation groups
+    ndcg_tolerance: float | None = None  # stop when the validation NDCG@K is >= this
     # [Predict]
     predict_files: list[str] = field(default_factory=list)
     predict_group_files: list[str] = field(default_factory=list)  # one group key per predict line (evaluate)
+    rank_cutoffs: list[int] = field(default_factory=list)  # NDCG@K / recall@K / precision@K cutoffs (evaluate)
     # [Distributed]
     mode: str = "auto"
     grad_reduce: str = "sum"
@@ -160,6 +170,18 @@ class FMRunConfig:
                         overlap_grads=self.overlap_grads, staleness=self.staleness,
                         stochastic_rounding=self.stochastic_rounding, dedup_chunk=self.dedup_chunk,
                         global_bias=self.global_bias)
+
+
+def _cutoffs(option: str, items: list, most: int) -> list:
+    """The ranking cutoffs of ``option``: 1 to ``most`` strictly ascending integers in [1, 4096]."""
+    try:
+        ks = [int(s) for s in items]
+    except ValueError:
+        ks = []
+    if not 1 <= len(ks) <= most or any(not 1 <= k <= 4096 for k in ks) or any(b <= a for a, b in zip(ks, ks[1:])):
+        what = "one integer" if most == 1 else "1 to %d strictly ascending integers" % most
+        raise ConfigError("%s must be %s in [1, 4096], got %s." % (option, what, ",".join(items)))
+    return ks
 
 
 def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunConfig:
@@ -281,6 +303,14 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
         raise ConfigError("validation_gauc needs validation_group_files.")
     if c.gauc_tolerance is not None and not c.validation_gauc:
         raise ConfigError("gauc_tolerance needs validation_gauc = true and validation_group_files.")
+    vn = read(TRAIN, "validation_ndcg", required=False)
+    if vn is not None:
+        c.validation_ndcg = _cutoffs("validation_ndcg", [vn.strip()], 1)[0]
+        if not c.validation_group_files:
+            raise ConfigError("validation_ndcg needs validation_group_files.")
+    c.ndcg_tolerance = opt(TRAIN, "ndcg_tolerance", float, c.ndcg_tolerance)
+    if c.ndcg_tolerance is not None and c.validation_ndcg is None:
+        raise ConfigError("ndcg_tolerance needs validation_ndcg and validation_group_files.")
 
     pf = read_list(PREDICT, "predict_files", required=False)
     if pf is not None:
@@ -290,6 +320,11 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
         c.predict_group_files = _expand(pgf, base_dir)
         if len(c.predict_files) != len(c.predict_group_files):
             raise ConfigError("The numbers of predict files and predict group files do not match.")
+    rc = read_list(PREDICT, "rank_cutoffs", required=False)
+    if rc is not None:
+        c.rank_cutoffs = _cutoffs("rank_cutoffs", rc, 4)
+        if not c.predict_group_files:
+            raise ConfigError("rank_cutoffs needs predict_group_files.")
 
     c.mode = opt(DISTRIBUTED, "mode", lambda s: s.strip().lower(), c.mode)
     c.grad_reduce = opt(DISTRIBUTED, "grad_reduce", lambda s: s.strip().lower(), c.grad_reduce)

@@ -10,6 +10,7 @@
 
 #include "../hash64.h"
 #include "../iso_hull.h"
+#include "../rank_table.h"
 #include "../score_key.h"
 #include "../topk_order.h"
 
@@ -402,6 +403,94 @@ void gauc(int n, long long G, const float* scores, const float* labels, const fl
   std::sort(kv.begin(), kv.end());
   if (weights) gauc_pass<double>(kv, G, labels, weights, nans, out, static_cast<double*>(rec));
   else gauc_pass<uint64_t>(kv, G, labels, weights, nans, out, static_cast<uint64_t*>(rec));
+}
+
+namespace {
+// The (group, key of vals, index) order of the examples; nans += the NaN values.
+std::vector<std::pair<uint64_t, uint32_t>> grouped_order(int n, long long G, const float* vals, const int* groups,
+                                                         uint64_t& nans) {
+  const std::vector<uint64_t> ks = keyed_scores(n, vals, nans);
+  std::vector<std::pair<uint64_t, uint32_t>> kv(ks.size());
+  for (int j = 0; j < n; ++j) {
+    const uint32_t g = static_cast<uint32_t>(groups[j]) < static_cast<uint64_t>(G) ? static_cast<uint32_t>(groups[j])
+                                                                                  : static_cast<uint32_t>(G - 1);
+    kv[j] = {(static_cast<uint64_t>(g) << 32) | (ks[j] >> 32), static_cast<uint32_t>(j)};
+  }
+  std::sort(kv.begin(), kv.end());
+  return kv;
+}
+
+// One pass per group over that order: a run [lb, ub) of equal keys in the group [first, end) occupies the ranks
+// a = end - ub + 1 .. b = end - lb, and every member with a positive gain adds gain (D[min(b, k)] - D[min(a - 1,
+// k)]) / (b - a + 1) to the cutoff's DCG -- into column dcg_col + 3 i of the group's record -- and, with hits,
+// (min(b, k) - min(a - 1, k)) / (b - a + 1) to its hits and 1 to P_g.
+void rank_pass(const std::vector<std::pair<uint64_t, uint32_t>>& kv, const std::vector<float>& gains, const double* D,
+               const int* k, int nk, int dcg_col, bool hits, double* per) {
+  const size_t n = kv.size(), ncol = 2 + 3 * static_cast<size_t>(nk);
+  for (size_t j = 0; j < n;) {
+    const uint32_t g = static_cast<uint32_t>(kv[j].first >> 32);
+    size_t end = j;
+    while (end < n && static_cast<uint32_t>(kv[end].first >> 32) == g) ++end;
+    double* r = per + ncol * g;
+    if (hits) r[0] = static_cast<double>(end - j);
+    while (j < end) {
+      size_t ub = j;
+      while (ub < end && kv[ub].first == kv[j].first) ++ub;
+      const long long a = static_cast<long long>(end - ub) + 1, b = static_cast<long long>(end - j);
+      const double len = static_cast<double>(b - a + 1);
+      for (; j < ub; ++j) {
+        const float gain = gains[kv[j].second];
+        if (!(gain > 0.f)) continue;
+        if (hits) r[1] += 1.0;
+        for (int i = 0; i < nk; ++i) {
+          if (a > k[i]) continue;
+          const long long lo = std::min<long long>(a - 1, k[i]), hi = std::min<long long>(b, k[i]);
+          r[dcg_col + 3 * i] += static_cast<double>(gain) * ((D[hi] - D[lo]) / len);
+          if (hits) r[4 + 3 * i] += static_cast<double>(hi - lo) / len;
+        }
+      }
+    }
+  }
+}
+}  // namespace
+
+bool rank_metrics(int n, long long G, const float* scores, const float* labels, const int* groups, const int* k,
+                  int nk, void* out, double* per) {
+  if (!rank_cutoffs_ok(k, nk)) return false;
+  static const std::vector<double> D = [] {
+    std::vector<double> d(kRankMaxCutoff + 1);
+    rank_dcg_table(d.data());
+    return d;
+  }();
+  const size_t ncol = 2 + 3 * static_cast<size_t>(nk);
+  std::fill(per, per + ncol * static_cast<size_t>(G), 0.0);
+  std::vector<float> gains(n > 0 ? n : 0);
+  for (int j = 0; j < n; ++j) gains[j] = labels[j] > 0.f ? labels[j] : 0.f;
+  uint64_t nans = 0, ideal_nans = 0;
+  rank_pass(grouped_order(n, G, scores, groups, nans), gains, D.data(), k, nk, 2, true, per);
+  rank_pass(grouped_order(n, G, gains.data(), groups, ideal_nans), gains, D.data(), k, nk, 3, false, per);
+  std::vector<double> sums(3 * static_cast<size_t>(nk), 0.0);
+  uint64_t ranked = 0, exs = 0;
+  for (long long g = 0; g < G; ++g) {
+    const double* r = per + ncol * static_cast<size_t>(g);
+    if (!(r[1] > 0)) continue;
+    ++ranked;
+    exs += static_cast<uint64_t>(r[0]);
+    for (int i = 0; i < nk; ++i) {
+      sums[3 * i] += r[2 + 3 * i] / r[3 + 3 * i];
+      sums[3 * i + 1] += r[4 + 3 * i] / r[1];
+      sums[3 * i + 2] += r[4 + 3 * i] / static_cast<double>(k[i]);
+    }
+  }
+  unsigned char* o = static_cast<unsigned char*>(out);
+  const uint64_t zero = 0;
+  std::memcpy(o, sums.data(), 8 * sums.size());
+  o += 8 * sums.size();
+  std::memcpy(o, &ranked, 8);
+  std::memcpy(o + 8, &exs, 8);
+  std::memcpy(o + 16, &nans, 8);
+  std::memcpy(o + 24, &zero, 8);
+  return true;
 }
 
 namespace {

@@ -65,6 +65,14 @@ void auc(int n, const float* scores, const float* labels, const float* weights, 
 void gauc(int n, long long G, const float* scores, const float* labels, const float* weights, const int* groups,
           void* out, void* rec);
 
+// Ranking statistics (hip/rank_metrics.hip: same definitions, the same discount table ../rank_table.h) of n scores
+// with group ids in [0, G) (ids outside it count as G - 1) at nk cutoffs k (rank_cutoffs_ok): per[G, 2 + 3 nk]
+// (fp64) = n_g, P_g, then DCG, IDCG, hits per cutoff, and out[3 nk + 4], 64-bit words = per cutoff the sums over
+// the ranked groups of NDCG_g, recall_g, precision_g (fp64), then the ranked groups, their examples, the NaN
+// scores, 0.  false: bad cutoffs (nothing is written).
+bool rank_metrics(int n, long long G, const float* scores, const float* labels, const int* groups, const int* k,
+                  int nk, void* out, double* per);
+
 // Exact isotonic regression (hip/isotonic.hip: same definition, same two modes) of n >= 1 scores, weights null
 // or all > 0: the blocks' first / last score lo, hi, weight W, positive weight Y (uint64 when weights is null,
 // else fp64 summed in sorted order) and value v = Y / W (fp64), [n] each; out[5] = blocks, total weight, positive

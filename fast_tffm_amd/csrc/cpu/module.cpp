@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../hash64.h"
+#include "../rank_table.h"
 #include "../topk_order.h"
 #include "bincsr.h"
 #include "kernels.h"
@@ -482,6 +483,20 @@ PYBIND11_MODULE(_fm_cpu, m) {
       },
       py::arg("n"), py::arg("G"), py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("groups"),
       py::arg("out"), py::arg("rec"));
+
+  m.def(
+      "rank_metrics",
+      [](int n, long long G, u64 scores, u64 labels, u64 groups, const std::vector<int>& cutoffs, u64 out, u64 per) {
+        py::gil_scoped_release nogil;
+        if (!fm::cpu::rank_metrics(n, G, P<const float>(scores), P<const float>(labels), P<const int>(groups),
+                                   cutoffs.data(), static_cast<int>(cutoffs.size()), P<void>(out), P<double>(per)))
+          throw std::invalid_argument("rank_metrics: 1 to 4 strictly ascending cutoffs in [1, 4096]");
+      },
+      py::arg("n"), py::arg("G"), py::arg("scores"), py::arg("labels"), py::arg("groups"), py::arg("cutoffs"),
+      py::arg("out"), py::arg("per"));
+  m.def(
+      "rank_dcg_table",  // D[0..4096] of ../rank_table.h, the table both rank_metrics implementations read
+      [](u64 out) { fm::rank_dcg_table(P<double>(out)); }, py::arg("out"));
 
   m.def(
       "isotonic",

@@ -30,6 +30,7 @@ using u64 = std::uintptr_t;
 #include "auc.hip"
 #include "isotonic.hip"
 #include "gauc.hip"
+#include "rank_metrics.hip"
 #include "shard.hip"
 #include "init.hip"
 #include "ckpt.hip"
@@ -375,6 +376,32 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       },
       py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("groups"), py::arg("n"), py::arg("G"),
       py::arg("out"), py::arg("rec"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
+
+  m.def(
+      "rank_metrics_workspace_bytes",
+      [](long long n, long long G) {
+        const size_t b = fm::rank_metrics_workspace_bytes(n, G);
+        if (!b) throw std::invalid_argument("rank_metrics: n must be in [0, 2^30) and num_groups in [1, 2^31)");
+        return b;
+      },
+      py::arg("n"), py::arg("G"));
+  m.def(
+      "rank_metrics",  // NDCG@k / recall@k / precision@k per group: [n_g, P_g, (DCG, IDCG, hits) per cutoff] into
+                       // per[G, 2 + 3 nk] (fp64) and the record [(sum NDCG, sum recall, sum precision) per cutoff,
+                       // ranked groups, examples in ranked groups, nan count, sort error word] into out[3 nk + 4]
+                       // (64-bit words); asynchronous (ops/kernels.py RankStats)
+      [](u64 scores, u64 labels, u64 groups, int n, long long G, const std::vector<int>& cutoffs, u64 out, u64 per,
+         u64 ws, size_t ws_bytes, u64 stream) {
+        const int rc = fm::launch_rank_metrics(P<const float>(scores), P<const float>(labels), P<const int>(groups), n,
+                                               G, cutoffs.data(), (int)cutoffs.size(), P<void>(out), P<void>(per),
+                                               P<void>(ws), ws_bytes, S(stream));
+        if (rc == -6) throw std::invalid_argument("rank_metrics: num_groups must be in [1, 2^31)");
+        if (rc == -7)
+          throw std::invalid_argument("rank_metrics: 1 to 4 strictly ascending cutoffs in [1, 4096]");
+        check(rc, "rank_metrics");
+      },
+      py::arg("scores"), py::arg("labels"), py::arg("groups"), py::arg("n"), py::arg("G"), py::arg("cutoffs"),
+      py::arg("out"), py::arg("per"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
 
   m.def(
       "gather_rows",

@@ -1069,6 +1069,134 @@ def gauc(scores: torch.Tensor, labels: torch.Tensor, groups: torch.Tensor, num_g
 
 
 # ---------------------------------------------------------------------------
+# ranking metrics per group: NDCG@k, recall@k, precision@k
+# ---------------------------------------------------------------------------
+RANK_MAX_CUTOFF = 4096  # csrc/rank_table.h
+RANK_MAX_CUTOFFS = 4
+
+
+def rank_cutoffs(cutoffs) -> tuple:
+    """``cutoffs`` as a tuple of ints; ``ValueError`` unless 1 to 4 strictly ascending integers in [1, 4096]."""
+    try:
+        ks = tuple(cutoffs)
+    except TypeError:
+        ks = (cutoffs,)
+    ok = 1 <= len(ks) <= RANK_MAX_CUTOFFS and all(
+        isinstance(k, int) and not isinstance(k, bool) and 1 <= k <= RANK_MAX_CUTOFF for k in ks)
+    if not ok or any(b <= a for a, b in zip(ks, ks[1:])):
+        raise ValueError("rank_metrics: cutoffs must be 1 to %d strictly ascending integers in [1, %d], got %r"
+                         % (RANK_MAX_CUTOFFS, RANK_MAX_CUTOFF, cutoffs))
+    return ks
+
+
+class RankStats(_SortedScoreRecord):
+    """The record of one ``rank_metrics`` call, on the op's device: ``3 nk + 4`` 64-bit words ``[per cutoff the
+    sums over the ranked groups of NDCG_g, recall_g, precision_g (fp64); ranked groups, examples in ranked
+    groups, NaN scores, sort error word]`` and ``groups``, the ``[G, 2 + 3 nk]`` float64 per-group ``(n_g, P_g,
+    then DCG, IDCG, hits per cutoff)``.  The readers synchronise with the launch chain on the GPU and raise when
+    its sort reported a failed look-back: never a number then."""
+
+    __slots__ = ("groups", "num_groups", "cutoffs")
+    _op, _result = "rank_metrics", "ranking metric"
+
+    def __init__(self, rec: torch.Tensor, groups: torch.Tensor, cutoffs: tuple, n: int, num_groups: int,
+                 done: "torch.cuda.Event | None" = None):
+        super().__init__(rec, False, n, done)
+        self.groups, self.num_groups, self.cutoffs = groups, num_groups, cutoffs
+
+    def stats(self) -> tuple:
+        """(the ``3 nk`` sums as floats, ranked groups, examples in ranked groups, nans) on the host."""
+        r = self._host_rec()
+        m = 3 * len(self.cutoffs)
+        i = r.tolist()
+        return r.view(torch.float64).tolist()[:m], i[m], i[m + 1], i[m + 2]
+
+    def _mean(self, k: int, which: int) -> float:
+        if isinstance(k, bool) or not isinstance(k, int):
+            raise ValueError(f"rank_metrics: a cutoff is an integer, got {k!r}")
+        if k not in self.cutoffs:
+            raise KeyError(f"rank_metrics: cutoff {k} is not one of this call's {self.cutoffs}")
+        sums, ranked, _, nans = self.stats()
+        if nans or not ranked:
+            return float("nan")
+        return sums[3 * self.cutoffs.index(k) + which] / ranked
+
+    def ndcg(self, k: int) -> float:
+        """Mean NDCG@k over the ranked groups; NaN when there is none or a score is NaN."""
+        return self._mean(k, 0)
+
+    def recall(self, k: int) -> float:
+        """Mean recall@k over the ranked groups (NaN as ``ndcg``)."""
+        return self._mean(k, 1)
+
+    def precision(self, k: int) -> float:
+        """Mean precision@k over the ranked groups (NaN as ``ndcg``)."""
+        return self._mean(k, 2)
+
+    def ranked_groups(self) -> int:
+        """Groups with a positive (the ones the means run over)."""
+        return self.stats()[1]
+
+    def coverage(self) -> float:
+        """Share of the examples that lie in ranked groups (NaN for an empty set)."""
+        return self.stats()[2] / self.n if self.n else float("nan")
+
+    def per_group(self) -> torch.Tensor:
+        """The ``[G, 2 + 3 nk]`` float64 tensor on the op's device; zeros for empty groups."""
+        self.stats()
+        return self.groups
+
+
+def rank_metrics_workspace(n: int, num_groups: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of ``rank_metrics`` for up to ``n`` scores in ``num_groups`` groups (GPU)."""
+    return torch.empty(int(native.hip().rank_metrics_workspace_bytes(int(n), int(num_groups))), dtype=torch.uint8,
+                       device=device)
+
+
+def rank_metrics(scores: torch.Tensor, labels: torch.Tensor, groups: torch.Tensor, num_groups: int, cutoffs, *,
+                 ws: torch.Tensor | None = None) -> RankStats:
+    """NDCG@k, recall@k and precision@k of every group and their means over the ranked groups.
+
+    ``groups``: int32 ids in ``[0, num_groups)``, one per score; ``cutoffs``: 1 to 4 strictly ascending integers
+    in [1, 4096].  The gain of an example is its label when that is > 0, else 0; it is positive iff ``label > 0``.
+    Within a group rank 1 is the highest score (``auc``'s score order); a run of equal scores at the ranks a..b
+    gives every member the run's mean position weight ``(C_k(b) - C_k(a - 1)) / (b - a + 1)`` -- the exact
+    expectation under uniformly random tie-breaking, independent of the input order.  Per group and cutoff:
+    DCG = sum gain * mean weight with c(j) = 1 / log2(j + 1), IDCG = the same with the gains as the scores, hits =
+    the expected number of positives in the top k; NDCG = DCG / IDCG, recall = hits / P_g, precision = hits / k.
+    A group is ranked iff it has a positive; each metric is the plain mean over the ranked groups -- NaN without
+    one or with a NaN score.  Everything is fp64 summed in a fixed order (bitwise the same run to run); the
+    discount sums come from one host-built table that GPU and CPU share.  There are no example weights.  GPU:
+    hip/rank_metrics.hip on the current stream (``ws``: reusable ``rank_metrics_workspace``; capturable after
+    one eager call on the device, as ``auc``); CPU: a sort and one pass per group.  ``n == 0`` launches nothing
+    (NaN).  Ids outside the range are an error with FM_DEBUG_CHECKS=1 and count as the last group without it.
+    """
+    ks = rank_cutoffs(cutoffs)
+    G = int(num_groups)
+    dev, n, _, _ = _sorted_score_inputs("rank_metrics", scores, labels, None, groups)
+    _check(1 <= G < 2**31, "rank_metrics: num_groups must be in [1, 2^31)")
+    if _DEBUG and n > 0 and not (scores.is_cuda and torch.cuda.is_current_stream_capturing()):
+        _check(bool(groups.min() >= 0) and bool(groups.max() < G), "groups: ids must be in [0, num_groups)")
+    nk = len(ks)
+    if n == 0:  # (host records: nothing is launched)
+        return RankStats(torch.zeros(3 * nk + 4, dtype=torch.int64), torch.zeros((G, 2 + 3 * nk), dtype=torch.float64),
+                         ks, 0, G)
+    rec = torch.empty(3 * nk + 4, dtype=torch.int64, device=dev)
+    per = torch.empty((G, 2 + 3 * nk), dtype=torch.float64, device=dev)
+    if _is_gpu(scores):
+        h = native.hip()
+        _, done = _sorted_score_launch(
+            "rank_metrics", dev, int(h.rank_metrics_workspace_bytes(n, G)), ws, lambda w: h.rank_metrics(
+                scores=_p(scores), labels=_p(labels), groups=_p(groups), n=n, G=G, cutoffs=list(ks), out=_p(rec),
+                per=_p(per), ws=_p(w), ws_bytes=w.numel(), stream=_stream(scores)))
+        return RankStats(rec, per, ks, n, G, done)
+    _check(ws is None, "rank_metrics: the workspace is a GPU argument")
+    native.cpu().rank_metrics(n=n, G=G, scores=_p(scores), labels=_p(labels), groups=_p(groups), cutoffs=list(ks),
+                              out=_p(rec), per=_p(per))
+    return RankStats(rec, per, ks, n, G)
+
+
+# ---------------------------------------------------------------------------
 # calibration: exact isotonic regression of (score, label, weight)
 # ---------------------------------------------------------------------------
 class IsotonicFit(_SortedScoreRecord):

@@ -41,7 +41,7 @@ from .data.reader import NativeTextReader, Prefetcher, ReaderState, TextBatchRea
 from .models.fm import FactorizationMachine
 from .data.groups import load_group_files
 from .calibration import FILE_NAME as CALIBRATION_FILE, CalibrationError, Calibrator, log_loss_sum_of_blocks
-from .ops.kernels import auc, check_device_errors, gauc, isotonic_fit
+from .ops.kernels import auc, check_device_errors, gauc, isotonic_fit, rank_metrics
 from .parallel.dist import DistContext, gather_dealt
 from .utils import checkpoint as ckpt
 from .utils.metrics import MetricsLogger
@@ -193,13 +193,27 @@ class Trainer:
         loss, v_auc, _ = self.validation_report(vb)
         return loss, v_auc
 
-    def validation_report(self, vb, want_auc: bool = True, groups=None) -> tuple:
+    def validation_report(self, vb, want_auc: bool = True, groups=None, *, rank_cutoffs=None,
+                          want_gauc: bool = True) -> tuple:
         """(loss, ROC AUC or None, ``GaucStats`` or None) of a labelled batch from ONE forward.  ``groups``:
         ``(this rank's int32 group ids of vb's examples, number of groups)`` for the grouped AUC
         (ops/kernels.py ``gauc``) of the same scores.  Multi-rank: the ids travel with the scores, labels
-        and weights (as their bit patterns: ``gather_dealt`` moves fp32 vectors and does no arithmetic)."""
+        and weights (as their bit patterns: ``gather_dealt`` moves fp32 vectors and does no arithmetic).
+        With ``rank_cutoffs`` (needs ``groups``) the tuple gains a fourth entry, the ``RankStats`` of
+        ``rank_metrics`` on the same gathered scores (no example weights enter it); ``want_gauc`` False leaves
+        the third entry None."""
         fo = self.model.forward(vb, loss=self.cfg.loss_type)
         loss = self._global_loss(float(fo.loss_sum), vb.B)
+        if rank_cutoffs is not None:
+            if groups is None:
+                raise ValueError("rank_cutoffs needs the group ids")
+            scores, labels, weights, ids = gather_dealt(
+                self.ctx if self.world > 1 else None,
+                [fo.pred[:vb.B].contiguous(), vb.labels, vb.weights, groups[0].view(torch.float32)])
+            ids = ids.view(torch.int32)
+            return (loss, auc(scores, labels, weights).value() if want_auc else None,
+                    gauc(scores, labels, ids, groups[1], weights) if want_gauc else None,
+                    rank_metrics(scores, labels, ids, groups[1], rank_cutoffs))
         if not want_auc and groups is None:
             return loss, None, None
         ids = None if groups is None else groups[0].view(torch.float32)
@@ -295,8 +309,14 @@ class Trainer:
                 last_loss, tprev = report(pending)
                 pending = None
                 if vb is not None:
-                    v_gauc = None
-                    if c.validation_gauc:
+                    v_gauc = v_ndcg = None
+                    if c.validation_ndcg is not None:
+                        v_loss, v_auc, gstats, rstats = self.validation_report(
+                            vb, c.validation_auc, self.val_groups, rank_cutoffs=(c.validation_ndcg,),
+                            want_gauc=c.validation_gauc)
+                        v_gauc = gstats.value() if c.validation_gauc else None
+                        v_ndcg = rstats.ndcg(c.validation_ndcg)
+                    elif c.validation_gauc:
                         v_loss, v_auc, gstats = self.validation_report(vb, c.validation_auc, self.val_groups)
                         v_gauc = gstats.value()
                     elif c.validation_auc:
@@ -311,6 +331,9 @@ class Trainer:
                     if v_gauc is not None:
                         self.print("validation gauc at step %d: %.8f" % (step_num, v_gauc))
                         metrics.log(step_num, force=True, validation_gauc=v_gauc)
+                    if v_ndcg is not None:
+                        self.print("validation ndcg@%d at step %d: %.8f" % (c.validation_ndcg, step_num, v_ndcg))
+                        metrics.log(step_num, force=True, validation_ndcg=v_ndcg)
                     if c.tolerance is not None and v_loss < c.tolerance:
                         self.print("Loss on validation data set is below tolerance. Training completed.")
                         ended_early = True
@@ -319,6 +342,9 @@ class Trainer:
                         ended_early = True
                     if c.gauc_tolerance is not None and v_gauc is not None and v_gauc >= c.gauc_tolerance:
                         self.print("GAUC on validation data set is above tolerance. Training completed.")
+                        ended_early = True
+                    if c.ndcg_tolerance is not None and v_ndcg is not None and v_ndcg >= c.ndcg_tolerance:
+                        self.print("NDCG on validation data set is above tolerance. Training completed.")
                         ended_early = True
                 check_device_errors(self.device)  # (kernels' sticky error word: fail before saving)
                 if c.log_dir:
@@ -457,7 +483,12 @@ class Trainer:
         one forward with unit weights, printed as ``evaluate <file>: examples N loss L auc A``.  With ``[Predict]
         predict_group_files`` the line goes on `` gauc G valid_groups V/T coverage C`` and ``<file>_gauc`` gets
         one line per group, ``key auc positives negatives examples``, by ascending AUC then key; the groups
-        without a positive or without a negative follow, by key, with ``nan``.  Returns the metrics per file.
+        without a positive or without a negative follow, by key, with ``nan``.  With ``[Predict] rank_cutoffs``
+        the line then goes on `` ndcg@K v recall@K v precision@K v`` per cutoff and `` ranked_groups V/T`` (the
+        means over the groups with a positive, ops/kernels.py ``rank_metrics``), and ``<file>_rank`` gets one
+        line per group, ``key examples positives`` then ``ndcg@K recall@K precision@K`` per cutoff, by
+        ascending NDCG at the first cutoff then key; the groups without a positive follow, by key, with
+        ``nan``.  Returns the metrics per file.
         Multi-rank runs deal the examples as ``predict`` does; rank 0 writes."""
         c = self.cfg
         if not self.restore():
@@ -478,7 +509,12 @@ class Trainer:
                 mine = _take(b, idx)
                 ids = None if ids is None else ids[idx].contiguous()
             groups = None if ids is None else (ids.to(self.device), gi.num_groups)
-            loss, v_auc, st = self.validation_report(mine.to(self.device), True, groups)
+            rst = None
+            if c.rank_cutoffs:
+                loss, v_auc, st, rst = self.validation_report(mine.to(self.device), True, groups,
+                                                              rank_cutoffs=tuple(c.rank_cutoffs))
+            else:
+                loss, v_auc, st = self.validation_report(mine.to(self.device), True, groups)
             res = {"examples": b.B, "loss": loss, "auc": v_auc}
             line = "evaluate %s: examples %d loss %.8f auc %.8f" % (path, b.B, loss, v_auc)
             if st is not None:
@@ -488,6 +524,17 @@ class Trainer:
                                                                         gi.num_groups, res["coverage"])
                 if self.rank == 0:
                     res["gauc_file"] = _write_group_aucs(path + "_gauc", gi, st.per_group().cpu().tolist())
+            if rst is not None:
+                for kk in rst.cutoffs:
+                    res.update({"ndcg@%d" % kk: rst.ndcg(kk), "recall@%d" % kk: rst.recall(kk),
+                                "precision@%d" % kk: rst.precision(kk)})
+                    line += " ndcg@%d %.8f recall@%d %.8f precision@%d %.8f" % (
+                        kk, res["ndcg@%d" % kk], kk, res["recall@%d" % kk], kk, res["precision@%d" % kk])
+                res["ranked_groups"] = rst.ranked_groups()
+                line += " ranked_groups %d/%d" % (res["ranked_groups"], gi.num_groups)
+                if self.rank == 0:
+                    res["rank_file"] = _write_group_ranks(path + "_rank", gi, rst.cutoffs,
+                                                          rst.per_group().cpu().tolist())
             self.print(line)
             results[path] = res
         return results
@@ -631,6 +678,24 @@ def _write_group_aucs(out: str, gi, recs: list) -> str:
         for invalid, a, key, g in sorted(rows):
             f.write("%s %s %s %s %d\n" % (key, "nan" if invalid else str(np.float32(a)), recs[g][1], recs[g][2],
                                           sizes[g]))
+    return out
+
+
+def _write_group_ranks(out: str, gi, cutoffs: tuple, recs: list) -> str:
+    """``<file>_rank`` of ``Trainer.evaluate`` from the per-group ``[n, P, (DCG, IDCG, hits) per cutoff]`` records
+    (ordered by the NDCG as written, in fp32: the last bits of an fp64 ratio order nothing)."""
+    rows = []
+    for g, r in enumerate(recs):
+        ranked = r[1] > 0
+        vals = []
+        for i, k in enumerate(cutoffs):
+            dcg, idcg, hits = r[2 + 3 * i:5 + 3 * i]
+            vals += [dcg / idcg, hits / r[1], hits / k] if ranked else [float("nan")] * 3
+        rows.append((not ranked, float(np.float32(vals[0])) if ranked else 0.0, gi.keys[g], g, vals))
+    with open(out, "w") as f:
+        for unranked, _, key, g, vals in sorted(rows):
+            f.write("%s %d %d %s\n" % (key, recs[g][0], recs[g][1],
+                                       " ".join("nan" if unranked else str(np.float32(v)) for v in vals)))
     return out
 
 
