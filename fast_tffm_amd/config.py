@@ -35,13 +35,21 @@ Extensions (new keys, all optional):
                                 after the GAUC / AUC / loss lines; one integer in [1, 4096]; needs
                                 validation_group_files), ndcg_tolerance = <float> (stop when the validation
                                 NDCG@K is >= it; needs validation_ndcg),
+                validation_ap = true|false (average precision of the validation scores, weighted like the loss,
+                                printed and logged after those lines; default false), ap_tolerance = <float>
+                                (stop when it is >= this; needs validation_ap and validation_files),
                 checkpoint_format = dense|sparse (sparse: a checkpoint stores only the rows that differ from
                                 their counter-based init, and restore regenerates the others; default dense)
   [Predict]     predict_group_files = <files> (one group key per line, parallel to predict_files: the
                                 ``evaluate`` task then reports the grouped AUC and writes <file>_gauc),
                 rank_cutoffs = <K>[,<K>...] (1 to 4 ascending integers in [1, 4096]: ``evaluate`` then also
                                 reports NDCG@K, recall@K and precision@K per group and writes <file>_rank; needs
-                                predict_group_files)
+                                predict_group_files),
+                threshold_metrics = true|false (``evaluate`` then also reports the average precision, KS and
+                                the best F1 and writes <file>_thresholds; default false),
+                precision_targets = <p>[,<p>...] / recall_targets = <r>[,<r>...] (0 to 4 values in (0, 1] each:
+                                ``evaluate`` reports the recall at precision >= p / the precision at recall >= r
+                                and the score thresholds in <file>_thresholds; either implies threshold_metrics)
   [Distributed] mode = auto|local|shard|dp|dp_dense, grad_reduce = sum|mean,
                 comm_dtype = auto|fp32|bf16 (row-sharded wire rows; auto = table storage dtype),
                 microbatches = 1|2|... (row-sharded step parts overlapping the exchange; default 1),
@@ -137,6 +145,11 @@ class FMRunConfig:
     predict_files: list[str] = field(default_factory=list)
     predict_group_files: list[str] = field(default_factory=list)  # one group key per predict line (evaluate)
     rank_cutoffs: list[int] = field(default_factory=list)  # NDCG@K / recall@K / precision@K cutoffs (evaluate)
+    validation_ap: bool = False          # report the average precision of the validation scores
+    ap_tolerance: float | None = None    # stop when the validation average precision is >= this
+    threshold_metrics: bool = False      # evaluate: average precision, KS, best F1 and <file>_thresholds
+    precision_targets: list[float] = field(default_factory=list)  # evaluate: recall at precision >= each
+    recall_targets: list[float] = field(default_factory=list)     # evaluate: precision at recall >= each
     # [Distributed]
     mode: str = "auto"
     grad_reduce: str = "sum"
@@ -182,6 +195,17 @@ def _cutoffs(option: str, items: list, most: int) -> list:
         what = "one integer" if most == 1 else "1 to %d strictly ascending integers" % most
         raise ConfigError("%s must be %s in [1, 4096], got %s." % (option, what, ",".join(items)))
     return ks
+
+
+def _targets(option: str, items: list) -> list:
+    """The precision / recall targets of ``option``: 1 to 4 numbers in (0, 1]."""
+    try:
+        ts = [float(s) for s in items]
+    except ValueError:
+        ts = []
+    if not 1 <= len(ts) <= 4 or any(not 0.0 < t <= 1.0 for t in ts):
+        raise ConfigError("%s must be 1 to 4 numbers in (0, 1], got %s." % (option, ",".join(items)))
+    return ts
 
 
 def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunConfig:
@@ -311,6 +335,10 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
     c.ndcg_tolerance = opt(TRAIN, "ndcg_tolerance", float, c.ndcg_tolerance)
     if c.ndcg_tolerance is not None and c.validation_ndcg is None:
         raise ConfigError("ndcg_tolerance needs validation_ndcg and validation_group_files.")
+    c.validation_ap = opt(TRAIN, "validation_ap", to_bool, c.validation_ap)
+    c.ap_tolerance = opt(TRAIN, "ap_tolerance", float, c.ap_tolerance)
+    if c.ap_tolerance is not None and not (c.validation_ap and c.validation_data_files):
+        raise ConfigError("ap_tolerance needs validation_ap = true and validation_files.")
 
     pf = read_list(PREDICT, "predict_files", required=False)
     if pf is not None:
@@ -325,6 +353,12 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
         c.rank_cutoffs = _cutoffs("rank_cutoffs", rc, 4)
         if not c.predict_group_files:
             raise ConfigError("rank_cutoffs needs predict_group_files.")
+    c.threshold_metrics = opt(PREDICT, "threshold_metrics", to_bool, c.threshold_metrics)
+    for key in ("precision_targets", "recall_targets"):
+        tg = read_list(PREDICT, key, required=False)
+        if tg is not None:
+            setattr(c, key, _targets(key, tg))
+            c.threshold_metrics = True
 
     c.mode = opt(DISTRIBUTED, "mode", lambda s: s.strip().lower(), c.mode)
     c.grad_reduce = opt(DISTRIBUTED, "grad_reduce", lambda s: s.strip().lower(), c.grad_reduce)

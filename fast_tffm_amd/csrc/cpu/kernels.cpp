@@ -4,6 +4,7 @@
 #include <cmath>
 #include <cstring>
 #include <numeric>
+#include <type_traits>
 #include <vector>
 
 #include <omp.h>
@@ -12,6 +13,7 @@
 #include "../iso_hull.h"
 #include "../rank_table.h"
 #include "../score_key.h"
+#include "../threshold_rule.h"
 #include "../topk_order.h"
 
 namespace fm {
@@ -336,6 +338,95 @@ void auc(int n, const float* scores, const float* labels, const float* weights, 
   std::sort(kv.begin(), kv.end());
   if (weights) auc_pass<double>(kv, labels, weights, nans, static_cast<double*>(out));
   else auc_pass<uint64_t>(kv, labels, weights, nans, static_cast<uint64_t*>(out));
+}
+
+namespace {
+// One pass over the (complemented key, index) order, from the highest score down: at the end of every run of
+// equal keys the candidate (TP, FP, last position) is tried for every selection (threshold_rule.h), then the
+// run's positives add their AP terms.  P and N are the sums of the same terms in the same order (a pass before).
+template <typename T>
+void threshold_pass(const std::vector<uint64_t>& kv, const float* labels, const float* weights, uint64_t nans,
+                    const thr::Targets& tg, T* out) {
+  const size_t n = kv.size();
+  const auto weight = [&](size_t j) {
+    return weights ? static_cast<T>(weights[static_cast<uint32_t>(kv[j])]) : static_cast<T>(1);
+  };
+  const auto positive = [&](size_t j) { return labels[static_cast<uint32_t>(kv[j])] > 0.f; };
+  T P = 0, N = 0;
+  for (size_t j = 0; j < n; ++j) (positive(j) ? P : N) += weight(j);
+  const double dP = static_cast<double>(P);
+  thr::Cand<T> sel[thr::kSel];
+  for (auto& c : sel) c = thr::no_cand<T>();
+  thr::Cand<T> rc[thr::kMaxTargets];  // the first candidate that passes each recall target
+  for (auto& c : rc) c = thr::no_cand<T>();
+  double ap = 0;
+  T tp = 0, fp = 0;
+  for (size_t j = 0; j < n;) {
+    const uint32_t key = static_cast<uint32_t>(kv[j] >> 32);
+    const size_t j0 = j;
+    for (; j < n && static_cast<uint32_t>(kv[j] >> 32) == key; ++j) (positive(j) ? tp : fp) += weight(j);
+    const T pp = tp + fp;
+    if (pp > static_cast<T>(0)) {
+      const thr::Cand<T> c{tp, fp, static_cast<int>(j - 1)};
+      const double dtp = static_cast<double>(tp), dpp = static_cast<double>(pp);
+      if (thr::ks_better(c, sel[0], P, N)) sel[0] = c;
+      if (thr::f1_better(c, sel[1], P)) sel[1] = c;
+      for (int i = 0; i < tg.np; ++i)
+        if (thr::precision_ok(dtp, dpp, tg.pt[i]) && thr::tp_better(c, sel[2 + i])) sel[2 + i] = c;
+      for (int i = 0; i < tg.nr; ++i)
+        if (rc[i].pos == thr::kNoPos && thr::recall_ok(dtp, dP, tg.rt[i])) rc[i] = c;
+    }
+    for (size_t i = j0; i < j; ++i) {
+      const T w = weight(i);
+      if (positive(i) && w > static_cast<T>(0))
+        ap = thr::ap_add(ap, static_cast<double>(w), static_cast<double>(tp), static_cast<double>(pp));
+    }
+  }
+  if constexpr (std::is_same<T, double>::value) {
+    out[0] = ap;
+  } else {
+    uint64_t bits;
+    std::memcpy(&bits, &ap, 8);
+    out[0] = bits;
+  }
+  out[1] = P;
+  out[2] = N;
+  thr::Cand<T> pts[thr::kPoints];
+  for (int s = 0; s < thr::kSel; ++s) pts[s] = sel[s];
+  for (int i = 0; i < thr::kMaxTargets; ++i) pts[thr::kSel + i] = rc[i];
+  for (int s = 0; s < thr::kPoints; ++s) {
+    const bool ok = pts[s].pos != thr::kNoPos;
+    T* o = out + thr::kPoint0 + 3 * s;
+    o[0] = ok ? pts[s].tp : static_cast<T>(0);
+    o[1] = ok ? pts[s].fp : static_cast<T>(0);
+    o[2] = ok ? static_cast<T>(score_key_bits(~static_cast<uint32_t>(kv[pts[s].pos] >> 32))) : static_cast<T>(0);
+  }
+  out[thr::kRecWords - 2] = static_cast<T>(nans);
+  out[thr::kRecWords - 1] = 0;
+}
+}  // namespace
+
+bool threshold_metrics(int n, const float* scores, const float* labels, const float* weights, const double* pt,
+                       int np, const double* rt, int nr, void* out) {
+  if (np < 0 || np > thr::kMaxTargets || nr < 0 || nr > thr::kMaxTargets) return false;
+  thr::Targets tg{};
+  tg.np = np;
+  tg.nr = nr;
+  for (int i = 0; i < np; ++i) {
+    if (!(pt[i] > 0.0 && pt[i] <= 1.0)) return false;
+    tg.pt[i] = pt[i];
+  }
+  for (int i = 0; i < nr; ++i) {
+    if (!(rt[i] > 0.0 && rt[i] <= 1.0)) return false;
+    tg.rt[i] = rt[i];
+  }
+  uint64_t nans = 0;
+  std::vector<uint64_t> kv = keyed_scores(n, scores, nans);
+  for (auto& x : kv) x ^= 0xffffffff00000000ull;  // the complemented key: from the highest score down
+  std::sort(kv.begin(), kv.end());
+  if (weights) threshold_pass<double>(kv, labels, weights, nans, tg, static_cast<double*>(out));
+  else threshold_pass<uint64_t>(kv, labels, weights, nans, tg, static_cast<uint64_t*>(out));
+  return true;
 }
 
 namespace {

@@ -58,6 +58,13 @@ void csr_rows(int B, const int* offsets, int* ex_of_occ);
 // scores, 0 -- uint64 when weights is null (exact), else fp64 summed in sorted order.
 void auc(int n, const float* scores, const float* labels, const float* weights, void* out);
 
+// Threshold metrics (hip/threshold_metrics.hip: same definitions, same two modes, the rules of
+// ../threshold_rule.h): out[thr::kRecWords], the record described there -- uint64 when weights is null (exact),
+// else fp64 summed from the highest score down; word 0 holds fp64 bits in both.  pt[np] / rt[nr]: the precision /
+// recall targets.  false: more than 4 targets of a kind or one outside (0, 1] (nothing is written).
+bool threshold_metrics(int n, const float* scores, const float* labels, const float* weights, const double* pt,
+                       int np, const double* rt, int nr, void* out);
+
 // Grouped AUC statistics (hip/gauc.hip: same definition, same two modes) of n scores with group ids in [0, G)
 // (ids outside it count as G - 1): rec[G, 3] = U2_g, P_g, N_g of every group (uint64 when weights is null, else
 // fp64 summed in (group, score) order) and out[6], 64-bit words = sum over the valid groups of W_g AUC_g (fp64),

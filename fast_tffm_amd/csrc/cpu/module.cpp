@@ -475,6 +475,19 @@ PYBIND11_MODULE(_fm_cpu, m) {
       py::arg("n"), py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("out"));
 
   m.def(
+      "threshold_metrics",
+      [](int n, u64 scores, u64 labels, u64 weights, const std::vector<double>& precision_targets,
+         const std::vector<double>& recall_targets, u64 out) {
+        py::gil_scoped_release nogil;
+        if (!fm::cpu::threshold_metrics(n, P<const float>(scores), P<const float>(labels), P<const float>(weights),
+                                        precision_targets.data(), static_cast<int>(precision_targets.size()),
+                                        recall_targets.data(), static_cast<int>(recall_targets.size()), P<void>(out)))
+          throw std::invalid_argument("threshold_metrics: 0 to 4 targets of a kind, each in (0, 1]");
+      },
+      py::arg("n"), py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("precision_targets"),
+      py::arg("recall_targets"), py::arg("out"));
+
+  m.def(
       "gauc",
       [](int n, long long G, u64 scores, u64 labels, u64 weights, u64 groups, u64 out, u64 rec) {
         py::gil_scoped_release nogil;

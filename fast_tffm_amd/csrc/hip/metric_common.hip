@@ -1,9 +1,10 @@
-// What the score-sorted metric chains (auc.hip, isotonic.hip, gauc.hip) share: the tile constants and the
-// ordered block scan, the score sort, the workspace cursor and the launchers' argument check, and the
-// two-channel prefix kernels of the AUC and the isotonic fit.
+// What the score-sorted metric chains (auc.hip, threshold_metrics.hip, isotonic.hip, gauc.hip) share: the tile
+// constants and the ordered block scan, the score sort, the workspace cursor and the launchers' argument check,
+// and the two-channel prefix kernels of the AUC, the threshold metrics and the isotonic fit.
 //
-// Score sort (launch_score_sort; scores ordered as score_key.h says):
-//   key:   key + example index per score, NaN count (integer atomic, one per wave);
+// Score sort (launch_score_sort; scores ordered as score_key.h says, or from the highest down on request):
+//   key:   key (complemented for the descending order) + example index per score, NaN count (integer atomic,
+//          one per wave);
 //   sort:  launch_radix_sort over all 32 key bits (radix_sort.hip: 4 passes of 8 bits, stable).
 // Prefix chain (launch_score_prefix: the sort, then, per sum type T and channel policy):
 //   tile:  per 2048-element tile of the sorted order the signed weight of every position (+w positive,
@@ -70,13 +71,16 @@ __device__ inline float signed_weight(const float* labels, const float* weights,
 }
 
 // ---- score sort -----------------------------------------------------------------------------------------
+// (kDesc: the complemented key, so that the ascending sort runs from the highest score down; ties stay in input
+// order.)
+template <bool kDesc = false>
 __global__ __launch_bounds__(kBlock) void auc_key_kernel(int n, const uint32_t* score_bits, uint32_t* keys, int* idx,
                                                          unsigned* nan_count) {
   unsigned nn = 0;
   for (int e = blockIdx.x * kBlock + threadIdx.x; e < n; e += gridDim.x * kBlock) {
     const uint32_t b = score_bits[e];
     nn += score_is_nan(b);
-    keys[e] = score_key(b);
+    keys[e] = kDesc ? ~score_key(b) : score_key(b);
     idx[e] = e;
   }
 #pragma unroll
@@ -93,12 +97,16 @@ struct ScoreSort {
 
 // Keys n >= 1 scores into keys / idx (the identity index), counts the NaNs and sorts into skeys / sidx,
 // asynchronously on st; sort_ws holds radix_sort_ws_bytes(n).  0, a hip error code or launch_radix_sort's.
+// descending: the keys are complemented (the highest score first).
 static int launch_score_sort(const float* scores, int n, uint32_t* keys, int* idx, uint32_t* skeys, int* sidx,
-                             unsigned* nan_count, void* sort_ws, hipStream_t st, ScoreSort& s) {
+                             unsigned* nan_count, void* sort_ws, hipStream_t st, ScoreSort& s,
+                             bool descending = false) {
   const hipError_t e = hipMemsetAsync(nan_count, 0, sizeof(unsigned), st);
   if (e != hipSuccess) return (int)e;
-  hipLaunchKernelGGL(auc_key_kernel, dim3(fill_grid(n, kBlock, 2048)), dim3(kBlock), 0, st, n,
-                     reinterpret_cast<const uint32_t*>(scores), keys, idx, nan_count);
+  const dim3 grid(fill_grid(n, kBlock, 2048));
+  const uint32_t* bits = reinterpret_cast<const uint32_t*>(scores);
+  if (descending) hipLaunchKernelGGL(auc_key_kernel<true>, grid, dim3(kBlock), 0, st, n, bits, keys, idx, nan_count);
+  else hipLaunchKernelGGL(auc_key_kernel<false>, grid, dim3(kBlock), 0, st, n, bits, keys, idx, nan_count);
   s = ScoreSort{skeys, sidx, nan_count, radix_sort_error(sort_ws, n)};
   return launch_radix_sort(keys, idx, skeys, sidx, n, 32, sort_ws, radix_sort_ws_bytes(n), st);
 }
@@ -136,6 +144,7 @@ struct Channels {
 };
 using AucChannels = Channels<false, false>;  // (negatives, positives), the negatives' prefix only
 using IsoChannels = Channels<true, true>;    // (all, positives), both prefixes
+using ThrChannels = Channels<false, true>;   // (negatives, positives), both prefixes
 
 template <typename T>
 struct PrefixArgs {
@@ -259,10 +268,11 @@ static PrefixLayout prefix_layout(WsCursor& c, int n, bool second_prefix) {
 }
 
 // The score sort and the prefix chain of channel policy C over the pieces l of ws; a = the kernels' arguments.
-// 0, or what launch_score_sort returned (nothing more is launched then).
+// 0, or what launch_score_sort returned (nothing more is launched then).  descending: from the highest score down.
 template <typename T, typename C>
 static int launch_score_prefix(const float* scores, const float* labels, const float* weights, int n, char* ws,
-                               const PrefixLayout& l, void* sort_ws, hipStream_t st, PrefixArgs<T>& a) {
+                               const PrefixLayout& l, void* sort_ws, hipStream_t st, PrefixArgs<T>& a,
+                               bool descending = false) {
   const size_t nt = (size_t)l.ntiles;
   T* tiles = reinterpret_cast<T*>(ws + l.tiles);
   T* misc = reinterpret_cast<T*>(ws + l.misc);
@@ -270,7 +280,7 @@ static int launch_score_prefix(const float* scores, const float* labels, const f
   const int se = launch_score_sort(scores, n, reinterpret_cast<uint32_t*>(ws + l.keys),
                                    reinterpret_cast<int*>(ws + l.idx), reinterpret_cast<uint32_t*>(ws + l.skeys),
                                    reinterpret_cast<int*>(ws + l.sidx), reinterpret_cast<unsigned*>(misc + 2), sort_ws,
-                                   st, s);
+                                   st, s, descending);
   if (se != 0) return se;
   constexpr bool k2 = C::kSecondPrefix;
   a = PrefixArgs<T>{n, l.ntiles, labels, weights, s.skeys, s.sidx, reinterpret_cast<uint32_t*>(ws + l.sv),

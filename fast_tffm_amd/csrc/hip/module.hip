@@ -28,6 +28,7 @@ using u64 = std::uintptr_t;
 #include "dedup.hip"
 #include "metric_common.hip"
 #include "auc.hip"
+#include "threshold_metrics.hip"
 #include "isotonic.hip"
 #include "gauc.hip"
 #include "rank_metrics.hip"
@@ -316,6 +317,29 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       },
       py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("n"), py::arg("out"), py::arg("ws"),
       py::arg("ws_bytes"), py::arg("stream"));
+
+  m.def(
+      "threshold_workspace_bytes",
+      [](long long n) {
+        const size_t b = fm::threshold_workspace_bytes(n);
+        if (!b) throw std::invalid_argument("threshold_metrics: n must be in [0, 2^30)");
+        return b;
+      },
+      py::arg("n"));
+  m.def(
+      "threshold_metrics",  // threshold metrics record (threshold_rule.h: 35 words, int64 when weights == 0, else
+                            // fp64) into out; asynchronous (ops/kernels.py ThresholdStats)
+      [](u64 scores, u64 labels, u64 weights, int n, const std::vector<double>& precision_targets,
+         const std::vector<double>& recall_targets, u64 out, u64 ws, size_t ws_bytes, u64 stream) {
+        const int rc = fm::launch_threshold(P<const float>(scores), P<const float>(labels), P<const float>(weights), n,
+                                            precision_targets.data(), (int)precision_targets.size(),
+                                            recall_targets.data(), (int)recall_targets.size(), P<void>(out),
+                                            P<void>(ws), ws_bytes, S(stream));
+        if (rc == -6) throw std::invalid_argument("threshold_metrics: 0 to 4 targets of a kind, each in (0, 1]");
+        check(rc, "threshold_metrics");
+      },
+      py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("n"), py::arg("precision_targets"),
+      py::arg("recall_targets"), py::arg("out"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
 
   m.def(
       "isotonic_workspace_bytes",

@@ -14,6 +14,7 @@ linear weights ``w`` are a separate fp32 vector (or column ``Kp`` of a packed
 from __future__ import annotations
 
 import os
+import struct
 from dataclasses import dataclass
 
 import torch
@@ -977,6 +978,152 @@ def auc(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None
     _check(ws is None, "auc: the workspace is a GPU argument")
     native.cpu().auc(n=n, scores=_p(scores), labels=_p(labels), weights=_p(weights), out=_p(rec))
     return AucStats(rec, weighted, n)
+
+
+# ---------------------------------------------------------------------------
+# threshold metrics: average precision, KS, best F1, operating points
+# ---------------------------------------------------------------------------
+_THR_MAX_TARGETS = 4                                 # csrc/threshold_rule.h: kMaxTargets
+_THR_POINT0, _THR_POINTS = 3, 2 + 2 * _THR_MAX_TARGETS  # ... kPoint0, kPoints
+_THR_WORDS = _THR_POINT0 + 3 * _THR_POINTS + 2       # ... kRecWords
+_NAN = float("nan")
+
+
+def threshold_targets(targets, what: str = "targets") -> tuple:
+    """``targets`` (a number or a sequence) as a tuple of floats: 0 to 4 values, each in (0, 1]."""
+    if isinstance(targets, (int, float)):
+        targets = (targets,)
+    t = tuple(float(x) for x in targets)
+    _check(len(t) <= _THR_MAX_TARGETS and all(0.0 < x <= 1.0 for x in t),
+           f"threshold_metrics: {what} must be 0 to {_THR_MAX_TARGETS} values in (0, 1]")
+    return t
+
+
+class ThresholdStats(_SortedScoreRecord):
+    """The record of one ``threshold_metrics`` call, on the op's device: 35 64-bit words (csrc/threshold_rule.h)
+    ``[AP numerator (fp64 bits), P, N, 10 points of (TP, FP, fp32 bits of the threshold): KS, best F1, the
+    precision targets, the recall targets, NaN scores, sort error word]`` -- int64 (unweighted: exact) or float64
+    (weighted).  The readers synchronise with the launch chain on the GPU and raise when the GPU sort reported a
+    failed look-back: never a number then."""
+
+    __slots__ = ("precision_targets", "recall_targets")
+    _op, _result = "threshold_metrics", "threshold metrics"
+
+    def __init__(self, rec: torch.Tensor, weighted: bool, n: int, precision_targets: tuple, recall_targets: tuple,
+                 done: "torch.cuda.Event | None" = None):
+        super().__init__(rec, weighted, n, done)
+        self.precision_targets, self.recall_targets = precision_targets, recall_targets
+
+    def stats(self) -> dict:
+        """The record on the host: ``ap_num`` (float), ``P``, ``N`` (Python ints unweighted, else floats),
+        ``nans``, and the points ``ks``, ``best_f1``, ``precision`` (one per target), ``recall`` (one per target):
+        each ``(TP, FP, threshold)`` or None when there is no such threshold."""
+        r = self._host_rec()
+        ap_num = float(r[:1].view(torch.float64)[0])
+        w = r.tolist()
+
+        def point(s: int):
+            tp, fp, bits = w[_THR_POINT0 + 3 * s: _THR_POINT0 + 3 * s + 3]
+            if not tp + fp > 0:
+                return None
+            return tp, fp, struct.unpack("<f", struct.pack("<I", int(bits)))[0]
+
+        np_, nr = len(self.precision_targets), len(self.recall_targets)
+        return {"ap_num": ap_num, "P": w[1], "N": w[2], "nans": int(w[-2]), "ks": point(0), "best_f1": point(1),
+                "precision": [point(2 + i) for i in range(np_)],
+                "recall": [point(2 + _THR_MAX_TARGETS + i) for i in range(nr)]}
+
+    @staticmethod
+    def _defined(st: dict) -> bool:
+        return not st["nans"] and st["P"] > 0 and st["N"] > 0
+
+    def ap(self) -> float:
+        """Average precision; NaN when a score is NaN or a class has no weight (undefined, not an error)."""
+        st = self.stats()
+        return st["ap_num"] / st["P"] if self._defined(st) else _NAN
+
+    def ks(self) -> tuple:
+        """(KS, its threshold): max over thresholds of |TP / P - FP / N|, at the highest such score."""
+        st = self.stats()
+        if not self._defined(st) or st["ks"] is None:
+            return _NAN, _NAN
+        tp, fp, t = st["ks"]
+        P, N = st["P"], st["N"]
+        return (abs(tp / P - fp / N) if self.weighted else abs(tp * N - fp * P) / (P * N)), t
+
+    @staticmethod
+    def _pr(point, P) -> tuple:
+        tp, fp, t = point
+        return t, tp / (tp + fp), tp / P
+
+    def best_f1(self) -> tuple:
+        """(F1, threshold, precision, recall) of the threshold with the greatest F1 (the highest such score)."""
+        st = self.stats()
+        if not self._defined(st) or st["best_f1"] is None:
+            return _NAN, _NAN, _NAN, _NAN
+        tp, fp, _ = st["best_f1"]
+        return (2 * tp / ((tp + fp) + st["P"]), *self._pr(st["best_f1"], st["P"]))
+
+    def _at(self, kind: str, targets: tuple, target: float) -> tuple:
+        _check(float(target) in targets, f"threshold_metrics: {target} is not one of the call's {kind} targets")
+        st = self.stats()
+        point = st[kind][targets.index(float(target))]
+        if not self._defined(st) or point is None:
+            return _NAN, _NAN, _NAN
+        return self._pr(point, st["P"])
+
+    def at_precision(self, target: float) -> tuple:
+        """(threshold, precision, recall) of the greatest recall with precision >= ``target`` (one of the call's
+        ``precision_targets``); NaNs when no threshold reaches it."""
+        return self._at("precision", self.precision_targets, target)
+
+    def at_recall(self, target: float) -> tuple:
+        """(threshold, precision, recall) of the highest threshold with recall >= ``target`` (one of the call's
+        ``recall_targets``)."""
+        return self._at("recall", self.recall_targets, target)
+
+
+def threshold_workspace(n: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of ``threshold_metrics`` for up to ``n`` scores (GPU)."""
+    return torch.empty(int(native.hip().threshold_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def threshold_metrics(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None = None, *,
+                      precision_targets=(), recall_targets=(), ws: torch.Tensor | None = None) -> ThresholdStats:
+    """Average precision, KS, best F1 and operating points of raw scores, with ``auc``'s conventions: an example
+    is positive iff ``label > 0``, ``weights`` None = all ones, scores compare as IEEE fp32 values (-0.0 == +0.0),
+    NaN scores are counted and make every value NaN, as does a class without weight.
+
+    Every distinct score t is a candidate threshold "positive iff score >= t" (a run of equal scores is never
+    split) with TP(t) / FP(t) the weight of the positives / negatives at or above it and PP = TP + FP > 0:
+    AP = (1 / P) sum over the positives of w_i TP(s_i) / PP(s_i) (scikit-learn's ``average_precision_score``);
+    KS = max |TP / P - FP / N|; best F1 = max 2 TP / (PP + P); a precision target pi (0 to 4, each in (0, 1]):
+    the greatest TP among the thresholds with TP >= pi PP; a recall target rho: the highest threshold with
+    TP >= rho P.  Equal maxima resolve to the highest score; a reported threshold is the run's score (+0.0 for
+    either zero).  Unweighted statistics are integers and every selection is exact (the same on GPU and CPU);
+    weighted ones are fp64 sums of non-negative terms from the highest score down, in a fixed order (bitwise the
+    same run to run).  GPU: hip/threshold_metrics.hip on the current stream (``ws``: reusable
+    ``threshold_workspace``; graph capture as for ``auc``); CPU: a sort and one pass.  ``n == 0`` launches nothing.
+    """
+    dev, n, weighted, rdt = _sorted_score_inputs("threshold_metrics", scores, labels, weights)
+    pt = threshold_targets(precision_targets, "precision_targets")
+    rt = threshold_targets(recall_targets, "recall_targets")
+    if _DEBUG and weighted and n > 0 and not (scores.is_cuda and torch.cuda.is_current_stream_capturing()):
+        _check(bool(weights.min() >= 0), "weights: must be >= 0")
+    if n == 0:
+        return ThresholdStats(torch.zeros(_THR_WORDS, dtype=rdt), weighted, 0, pt, rt)  # (nothing is launched)
+    rec = torch.empty(_THR_WORDS, dtype=rdt, device=dev)
+    if _is_gpu(scores):
+        h = native.hip()
+        _, done = _sorted_score_launch(
+            "threshold_metrics", dev, int(h.threshold_workspace_bytes(n)), ws, lambda w: h.threshold_metrics(
+                scores=_p(scores), labels=_p(labels), weights=_p(weights), n=n, precision_targets=list(pt),
+                recall_targets=list(rt), out=_p(rec), ws=_p(w), ws_bytes=w.numel(), stream=_stream(scores)))
+        return ThresholdStats(rec, weighted, n, pt, rt, done)
+    _check(ws is None, "threshold_metrics: the workspace is a GPU argument")
+    native.cpu().threshold_metrics(n=n, scores=_p(scores), labels=_p(labels), weights=_p(weights),
+                                   precision_targets=list(pt), recall_targets=list(rt), out=_p(rec))
+    return ThresholdStats(rec, weighted, n, pt, rt)
 
 
 # ---------------------------------------------------------------------------

@@ -8,14 +8,16 @@ Reference behaviour kept (run_tffm.py:10-90, :213-231):
   tolerance. Training completed."), checkpoint (CheckpointSaverHook); with ``validation_auc`` (new) also
   ``validation auc at step %d: %.8f`` and an early stop at ``auc_tolerance``; with ``validation_gauc`` (new,
   needs ``validation_group_files``) then ``validation gauc at step %d: %.8f`` -- the grouped AUC of the same
-  forward's scores -- and an early stop at ``gauc_tolerance``;
+  forward's scores -- and an early stop at ``gauc_tolerance``; with ``validation_ap`` (new) then ``validation ap
+  at step %d: %.8f`` -- the average precision of the same scores -- and an early stop at ``ap_tolerance``;
 * automatic restore of the latest checkpoint in ``log_dir`` (MonitoredTrainingSession);
 * end: ``Average speed:  <ex/s>  ex/s`` and ``Model saved to  <log_dir>``;
 * ``-t FILE``: chrome-trace timeline (reference: first step only; here the
   first few steps after one warm-up step);
 * predict: ``<predict_file>_score`` with one raw score (logit) per line;
 * evaluate (new): loss, ROC AUC and -- with ``predict_group_files`` -- grouped AUC of a checkpoint on the
-  labelled predict files, and ``<predict_file>_gauc`` with one line per group;
+  labelled predict files, and ``<predict_file>_gauc`` with one line per group; with ``threshold_metrics`` or
+  targets also average precision, KS, best F1, the targets' operating points and ``<predict_file>_thresholds``;
 * calibrate (new): an exact isotonic fit of the checkpoint's scores on the validation files, written as
   ``calibration.json`` into the checkpoint's directory; ``predict --calibrated`` then also writes
   ``<predict_file>_prob`` with one calibrated probability per line.
@@ -41,7 +43,7 @@ from .data.reader import NativeTextReader, Prefetcher, ReaderState, TextBatchRea
 from .models.fm import FactorizationMachine
 from .data.groups import load_group_files
 from .calibration import FILE_NAME as CALIBRATION_FILE, CalibrationError, Calibrator, log_loss_sum_of_blocks
-from .ops.kernels import auc, check_device_errors, gauc, isotonic_fit, rank_metrics
+from .ops.kernels import auc, check_device_errors, gauc, isotonic_fit, rank_metrics, threshold_metrics
 from .parallel.dist import DistContext, gather_dealt
 from .utils import checkpoint as ckpt
 from .utils.metrics import MetricsLogger
@@ -194,16 +196,25 @@ class Trainer:
         return loss, v_auc
 
     def validation_report(self, vb, want_auc: bool = True, groups=None, *, rank_cutoffs=None,
-                          want_gauc: bool = True) -> tuple:
+                          want_gauc: bool = True, thresholds=None) -> tuple:
         """(loss, ROC AUC or None, ``GaucStats`` or None) of a labelled batch from ONE forward.  ``groups``:
         ``(this rank's int32 group ids of vb's examples, number of groups)`` for the grouped AUC
         (ops/kernels.py ``gauc``) of the same scores.  Multi-rank: the ids travel with the scores, labels
         and weights (as their bit patterns: ``gather_dealt`` moves fp32 vectors and does no arithmetic).
         With ``rank_cutoffs`` (needs ``groups``) the tuple gains a fourth entry, the ``RankStats`` of
         ``rank_metrics`` on the same gathered scores (no example weights enter it); ``want_gauc`` False leaves
-        the third entry None."""
+        the third entry None.  With ``thresholds`` = ``(precision targets, recall targets)`` the tuple gains
+        a last entry, the ``ThresholdStats`` of ``threshold_metrics`` on the same gathered scores, labels and
+        weights."""
         fo = self.model.forward(vb, loss=self.cfg.loss_type)
         loss = self._global_loss(float(fo.loss_sum), vb.B)
+
+        def thr(scores, labels, weights) -> tuple:
+            if thresholds is None:
+                return ()
+            return (threshold_metrics(scores, labels, weights, precision_targets=thresholds[0],
+                                      recall_targets=thresholds[1]),)
+
         if rank_cutoffs is not None:
             if groups is None:
                 raise ValueError("rank_cutoffs needs the group ids")
@@ -213,15 +224,15 @@ class Trainer:
             ids = ids.view(torch.int32)
             return (loss, auc(scores, labels, weights).value() if want_auc else None,
                     gauc(scores, labels, ids, groups[1], weights) if want_gauc else None,
-                    rank_metrics(scores, labels, ids, groups[1], rank_cutoffs))
-        if not want_auc and groups is None:
+                    rank_metrics(scores, labels, ids, groups[1], rank_cutoffs)) + thr(scores, labels, weights)
+        if not want_auc and groups is None and thresholds is None:
             return loss, None, None
         ids = None if groups is None else groups[0].view(torch.float32)
         scores, labels, weights, ids = gather_dealt(self.ctx if self.world > 1 else None,
                                                     [fo.pred[:vb.B].contiguous(), vb.labels, vb.weights, ids])
         v_auc = auc(scores, labels, weights).value() if want_auc else None
         st = None if groups is None else gauc(scores, labels, ids.view(torch.int32), groups[1], weights)
-        return loss, v_auc, st
+        return (loss, v_auc, st) + thr(scores, labels, weights)
 
     # ------------------------------------------------------------------
     def train(self) -> dict:
@@ -309,20 +320,26 @@ class Trainer:
                 last_loss, tprev = report(pending)
                 pending = None
                 if vb is not None:
-                    v_gauc = v_ndcg = None
+                    v_gauc = v_ndcg = v_ap = None
+                    want_thr = ((), ()) if c.validation_ap else None  # (no targets: the average precision)
                     if c.validation_ndcg is not None:
-                        v_loss, v_auc, gstats, rstats = self.validation_report(
+                        v_loss, v_auc, gstats, rstats, *tstats = self.validation_report(
                             vb, c.validation_auc, self.val_groups, rank_cutoffs=(c.validation_ndcg,),
-                            want_gauc=c.validation_gauc)
+                            want_gauc=c.validation_gauc, thresholds=want_thr)
                         v_gauc = gstats.value() if c.validation_gauc else None
                         v_ndcg = rstats.ndcg(c.validation_ndcg)
                     elif c.validation_gauc:
-                        v_loss, v_auc, gstats = self.validation_report(vb, c.validation_auc, self.val_groups)
+                        v_loss, v_auc, gstats, *tstats = self.validation_report(vb, c.validation_auc, self.val_groups,
+                                                                                thresholds=want_thr)
                         v_gauc = gstats.value()
+                    elif c.validation_ap:
+                        v_loss, v_auc, _, *tstats = self.validation_report(vb, c.validation_auc, thresholds=want_thr)
                     elif c.validation_auc:
                         v_loss, v_auc = self.validation_metrics(vb)
                     else:
                         v_loss, v_auc = self.validation_loss(vb), None
+                    if c.validation_ap:
+                        v_ap = tstats[0].ap()
                     self.print("validation loss at step %d: %.8f" % (step_num, v_loss))
                     metrics.log(step_num, force=True, validation_loss=v_loss)
                     if v_auc is not None:
@@ -334,6 +351,9 @@ class Trainer:
                     if v_ndcg is not None:
                         self.print("validation ndcg@%d at step %d: %.8f" % (c.validation_ndcg, step_num, v_ndcg))
                         metrics.log(step_num, force=True, validation_ndcg=v_ndcg)
+                    if v_ap is not None:
+                        self.print("validation ap at step %d: %.8f" % (step_num, v_ap))
+                        metrics.log(step_num, force=True, validation_ap=v_ap)
                     if c.tolerance is not None and v_loss < c.tolerance:
                         self.print("Loss on validation data set is below tolerance. Training completed.")
                         ended_early = True
@@ -345,6 +365,10 @@ class Trainer:
                         ended_early = True
                     if c.ndcg_tolerance is not None and v_ndcg is not None and v_ndcg >= c.ndcg_tolerance:
                         self.print("NDCG on validation data set is above tolerance. Training completed.")
+                        ended_early = True
+                    if c.ap_tolerance is not None and v_ap is not None and v_ap >= c.ap_tolerance:
+                        self.print("Average precision on validation data set is above tolerance. Training "
+                                   "completed.")
                         ended_early = True
                 check_device_errors(self.device)  # (kernels' sticky error word: fail before saving)
                 if c.log_dir:
@@ -488,7 +512,10 @@ class Trainer:
         means over the groups with a positive, ops/kernels.py ``rank_metrics``), and ``<file>_rank`` gets one
         line per group, ``key examples positives`` then ``ndcg@K recall@K precision@K`` per cutoff, by
         ascending NDCG at the first cutoff then key; the groups without a positive follow, by key, with
-        ``nan``.  Returns the metrics per file.
+        ``nan``.  With ``[Predict] threshold_metrics`` (or targets) the line ends with `` ap A ks K best_f1 F``,
+        then `` recall@p<pi> R`` per precision target and `` precision@r<rho> Q`` per recall target
+        (ops/kernels.py ``threshold_metrics``), and ``<file>_thresholds`` gets one line per operating point.
+        Returns the metrics per file.
         Multi-rank runs deal the examples as ``predict`` does; rank 0 writes."""
         c = self.cfg
         if not self.restore():
@@ -510,11 +537,14 @@ class Trainer:
                 ids = None if ids is None else ids[idx].contiguous()
             groups = None if ids is None else (ids.to(self.device), gi.num_groups)
             rst = None
+            want_thr = (tuple(c.precision_targets), tuple(c.recall_targets)) if c.threshold_metrics else None
             if c.rank_cutoffs:
-                loss, v_auc, st, rst = self.validation_report(mine.to(self.device), True, groups,
-                                                              rank_cutoffs=tuple(c.rank_cutoffs))
+                loss, v_auc, st, rst, *tst = self.validation_report(mine.to(self.device), True, groups,
+                                                                    rank_cutoffs=tuple(c.rank_cutoffs),
+                                                                    thresholds=want_thr)
             else:
-                loss, v_auc, st = self.validation_report(mine.to(self.device), True, groups)
+                loss, v_auc, st, *tst = self.validation_report(mine.to(self.device), True, groups,
+                                                               thresholds=want_thr)
             res = {"examples": b.B, "loss": loss, "auc": v_auc}
             line = "evaluate %s: examples %d loss %.8f auc %.8f" % (path, b.B, loss, v_auc)
             if st is not None:
@@ -535,6 +565,18 @@ class Trainer:
                 if self.rank == 0:
                     res["rank_file"] = _write_group_ranks(path + "_rank", gi, rst.cutoffs,
                                                           rst.per_group().cpu().tolist())
+            if tst:
+                ts = tst[0]
+                res.update(ap=ts.ap(), ks=ts.ks()[0], best_f1=ts.best_f1()[0])
+                line += " ap %.8f ks %.8f best_f1 %.8f" % (res["ap"], res["ks"], res["best_f1"])
+                for t in ts.precision_targets:
+                    res["recall@p%g" % t] = ts.at_precision(t)[2]
+                    line += " recall@p%g %.8f" % (t, res["recall@p%g" % t])
+                for t in ts.recall_targets:
+                    res["precision@r%g" % t] = ts.at_recall(t)[1]
+                    line += " precision@r%g %.8f" % (t, res["precision@r%g" % t])
+                if self.rank == 0:
+                    res["thresholds_file"] = _write_thresholds(path + "_thresholds", ts)
             self.print(line)
             results[path] = res
         return results
@@ -678,6 +720,27 @@ def _write_group_aucs(out: str, gi, recs: list) -> str:
         for invalid, a, key, g in sorted(rows):
             f.write("%s %s %s %s %d\n" % (key, "nan" if invalid else str(np.float32(a)), recs[g][1], recs[g][2],
                                           sizes[g]))
+    return out
+
+
+def _write_thresholds(out: str, ts) -> str:
+    """``<file>_thresholds`` of ``Trainer.evaluate``: one line per operating point, ``kind target threshold
+    precision recall f1 tp fp`` -- ``ks``, ``best_f1`` (target ``-``), a ``precision`` row per precision target
+    and a ``recall`` row per recall target; floats as ``predict`` prints scores, ``nan`` where no threshold
+    qualifies."""
+    st = ts.stats()
+    ok = ts._defined(st)
+    rows = [("ks", "-", st["ks"]), ("best_f1", "-", st["best_f1"])]
+    rows += [("precision", "%g" % t, p) for t, p in zip(ts.precision_targets, st["precision"])]
+    rows += [("recall", "%g" % t, p) for t, p in zip(ts.recall_targets, st["recall"])]
+    with open(out, "w") as f:
+        for kind, target, point in rows:
+            vals, counts = [float("nan")] * 4, ["nan", "nan"]
+            if ok and point is not None:
+                tp, fp, t = point
+                vals = [t, tp / (tp + fp), tp / st["P"], 2 * tp / ((tp + fp) + st["P"])]
+                counts = [str(int(v)) if float(v).is_integer() else repr(float(v)) for v in (tp, fp)]
+            f.write("%s %s %s %s\n" % (kind, target, " ".join(str(np.float32(v)) for v in vals), " ".join(counts)))
     return out
 
 
