@@ -14,7 +14,9 @@ Extensions: --device {auto,cpu,cuda}, --mode {auto,local,shard,dp,dp_dense},
 FILE by the score of both taken together: ``<file>_recommend``, trainer.Trainer.recommend), the task
 ``evaluate CONFIG`` (loss and ROC AUC of the checkpoint on the labelled predict files and, with ``[Predict]
 predict_group_files``, the grouped AUC and ``<file>_gauc``, with ``rank_cutoffs`` NDCG@k / recall@k /
-precision@k and ``<file>_rank``: trainer.Trainer.evaluate), the task ``calibrate
+precision@k and ``<file>_rank``, with ``auc_interval`` DeLong's standard error and confidence interval of the
+AUC, with ``baseline_score_files`` DeLong's paired test against another model's ``predict`` scores:
+trainer.Trainer.evaluate), the task ``calibrate
 CONFIG`` (an exact isotonic fit of the checkpoint's scores on ``[Train] validation_files``, written as
 ``calibration.json`` into the checkpoint's directory: trainer.Trainer.calibrate; ``predict CONFIG --calibrated``
 then also writes ``<file>_prob``), and the task

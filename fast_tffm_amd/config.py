@@ -49,7 +49,12 @@ Extensions (new keys, all optional):
                                 the best F1 and writes <file>_thresholds; default false),
                 precision_targets = <p>[,<p>...] / recall_targets = <r>[,<r>...] (0 to 4 values in (0, 1] each:
                                 ``evaluate`` reports the recall at precision >= p / the precision at recall >= r
-                                and the score thresholds in <file>_thresholds; either implies threshold_metrics)
+                                and the score thresholds in <file>_thresholds; either implies threshold_metrics),
+                auc_interval = <L> (a confidence level in (0, 1): ``evaluate`` then also reports DeLong's standard
+                                error of the AUC and the interval at that level),
+                baseline_score_files = <files> (one raw score per line as ``predict`` writes them, parallel to
+                                predict_files: ``evaluate`` then also reports the baseline's AUC and DeLong's
+                                paired test of the difference)
   [Distributed] mode = auto|local|shard|dp|dp_dense, grad_reduce = sum|mean,
                 comm_dtype = auto|fp32|bf16 (row-sharded wire rows; auto = table storage dtype),
                 microbatches = 1|2|... (row-sharded step parts overlapping the exchange; default 1),
@@ -150,6 +155,8 @@ class FMRunConfig:
     threshold_metrics: bool = False      # evaluate: average precision, KS, best F1 and <file>_thresholds
     precision_targets: list[float] = field(default_factory=list)  # evaluate: recall at precision >= each
     recall_targets: list[float] = field(default_factory=list)     # evaluate: precision at recall >= each
+    auc_interval: float | None = None    # evaluate: DeLong confidence interval of the AUC at this level
+    baseline_score_files: list[str] = field(default_factory=list)  # evaluate: paired DeLong test against these scores
     # [Distributed]
     mode: str = "auto"
     grad_reduce: str = "sum"
@@ -359,6 +366,19 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
         if tg is not None:
             setattr(c, key, _targets(key, tg))
             c.threshold_metrics = True
+    ai = read(PREDICT, "auc_interval", required=False)
+    if ai is not None:
+        try:
+            c.auc_interval = float(ai)
+        except ValueError:
+            c.auc_interval = float("nan")
+        if not 0.0 < c.auc_interval < 1.0:
+            raise ConfigError(f"auc_interval must be a confidence level in (0, 1), got {ai.strip()}")
+    bsf = read_list(PREDICT, "baseline_score_files", required=False)
+    if bsf is not None:
+        c.baseline_score_files = _expand(bsf, base_dir)
+        if len(c.predict_files) != len(c.baseline_score_files):
+            raise ConfigError("The numbers of predict files and baseline score files do not match.")
 
     c.mode = opt(DISTRIBUTED, "mode", lambda s: s.strip().lower(), c.mode)
     c.grad_reduce = opt(DISTRIBUTED, "grad_reduce", lambda s: s.strip().lower(), c.grad_reduce)

@@ -341,6 +341,71 @@ void auc(int n, const float* scores, const float* labels, const float* weights, 
 }
 
 namespace {
+// Placement of every example from one pass over the (key, index) order: in a run of equal keys with rp positives
+// and rn negatives after nlt negatives and plt positives, a positive gets nlt + (nlt + rn) and a negative
+// (P - plt - rp) + (P - plt).  Returns U2, the sum of the positives' placements.
+uint64_t delong_place(const std::vector<uint64_t>& kv, const float* labels, uint64_t P, uint32_t* pl) {
+  const size_t n = kv.size();
+  uint64_t u2 = 0, nlt = 0, plt = 0;
+  for (size_t j = 0; j < n;) {
+    const uint32_t key = static_cast<uint32_t>(kv[j] >> 32);
+    const size_t j0 = j;
+    uint64_t rp = 0, rn = 0;
+    for (; j < n && static_cast<uint32_t>(kv[j] >> 32) == key; ++j)
+      (labels[static_cast<uint32_t>(kv[j])] > 0.f ? rp : rn) += 1;
+    const uint64_t a = nlt + (nlt + rn), b = (P - plt - rp) + (P - plt);
+    for (size_t i = j0; i < j; ++i) {
+      const uint32_t e = static_cast<uint32_t>(kv[i]);
+      pl[e] = static_cast<uint32_t>(labels[e] > 0.f ? a : b);
+    }
+    u2 += rp * a;
+    nlt += rn;
+    plt += rp;
+  }
+  return u2;
+}
+}  // namespace
+
+void delong_moments(int n, const uint32_t* pl_a, const uint32_t* pl_b, const float* labels, uint64_t* out) {
+  for (int w = 0; w < 12; ++w) out[w] = 0;
+  const auto add = [&](int w, uint32_t x, uint32_t y) {
+    const uint64_t t = static_cast<uint64_t>(x) * y;
+    out[w] += t >> 32;
+    out[w + 1] += t & 0xffffffffull;
+  };
+  for (int e = 0; e < n; ++e) {
+    const int c = labels[e] > 0.f ? 0 : 2;
+    add(c, pl_a[e], pl_a[e]);
+    if (pl_b) {
+      add(4 + c, pl_b[e], pl_b[e]);
+      add(8 + c, pl_a[e], pl_b[e]);
+    }
+  }
+}
+
+void auc_delong(int n, const float* scores_a, const float* scores_b, const float* labels, uint64_t* out) {
+  uint64_t P = 0;
+  for (int e = 0; e < n; ++e) P += labels[e] > 0.f;
+  std::vector<uint32_t> pl[2];
+  uint64_t u2[2] = {0, 0}, nans[2] = {0, 0};
+  for (int m = 0; m < (scores_b ? 2 : 1); ++m) {
+    std::vector<uint64_t> kv = keyed_scores(n, m ? scores_b : scores_a, nans[m]);
+    std::sort(kv.begin(), kv.end());
+    pl[m].resize(kv.size());
+    u2[m] = delong_place(kv, labels, P, pl[m].data());
+  }
+  out[0] = u2[0];
+  out[1] = u2[1];
+  out[2] = P;
+  out[3] = static_cast<uint64_t>(n > 0 ? n : 0) - P;
+  delong_moments(n, pl[0].data(), scores_b ? pl[1].data() : nullptr, labels, out + 4);
+  out[16] = nans[0];
+  out[17] = nans[1];
+  out[18] = scores_b ? 1 : 0;
+  out[19] = 0;
+}
+
+namespace {
 // One pass over the (complemented key, index) order, from the highest score down: at the end of every run of
 // equal keys the candidate (TP, FP, last position) is tried for every selection (threshold_rule.h), then the
 // run's positives add their AP terms.  P and N are the sums of the same terms in the same order (a pass before).

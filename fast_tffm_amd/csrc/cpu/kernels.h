@@ -58,6 +58,15 @@ void csr_rows(int B, const int* offsets, int* ex_of_occ);
 // scores, 0 -- uint64 when weights is null (exact), else fp64 summed in sorted order.
 void auc(int n, const float* scores, const float* labels, const float* weights, void* out);
 
+// DeLong statistics (hip/auc_delong.hip: same definitions, same record) of one model (scores_b null) or two on the
+// same examples, unweighted: out[20] (uint64) = U2_a, U2_b, P, N, (hi, lo) of M_pos / M_neg of (a, a), (b, b),
+// (a, b), NaN scores of a, of b, has_b, 0.
+void auc_delong(int n, const float* scores_a, const float* scores_b, const float* labels, uint64_t* out);
+
+// The 12 moment words of n placements (pl_b null: (a, a) only, the rest 0): every product t adds t >> 32 to its
+// hi word and t & 0xffffffff to its lo word.
+void delong_moments(int n, const uint32_t* pl_a, const uint32_t* pl_b, const float* labels, uint64_t* out);
+
 // Threshold metrics (hip/threshold_metrics.hip: same definitions, same two modes, the rules of
 // ../threshold_rule.h): out[thr::kRecWords], the record described there -- uint64 when weights is null (exact),
 // else fp64 summed from the highest score down; word 0 holds fp64 bits in both.  pt[np] / rt[nr]: the precision /

@@ -475,6 +475,24 @@ PYBIND11_MODULE(_fm_cpu, m) {
       py::arg("n"), py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("out"));
 
   m.def(
+      "auc_delong",
+      [](int n, u64 scores_a, u64 scores_b, u64 labels, u64 out) {
+        py::gil_scoped_release nogil;
+        fm::cpu::auc_delong(n, P<const float>(scores_a), P<const float>(scores_b), P<const float>(labels),
+                            P<uint64_t>(out));
+      },
+      py::arg("n"), py::arg("scores_a"), py::arg("scores_b"), py::arg("labels"), py::arg("out"));
+
+  m.def(
+      "delong_moments",
+      [](int n, u64 pl_a, u64 pl_b, u64 labels, u64 out) {
+        py::gil_scoped_release nogil;
+        fm::cpu::delong_moments(n, P<const uint32_t>(pl_a), P<const uint32_t>(pl_b), P<const float>(labels),
+                                P<uint64_t>(out));
+      },
+      py::arg("n"), py::arg("pl_a"), py::arg("pl_b"), py::arg("labels"), py::arg("out"));
+
+  m.def(
       "threshold_metrics",
       [](int n, u64 scores, u64 labels, u64 weights, const std::vector<double>& precision_targets,
          const std::vector<double>& recall_targets, u64 out) {

@@ -28,6 +28,7 @@ using u64 = std::uintptr_t;
 #include "dedup.hip"
 #include "metric_common.hip"
 #include "auc.hip"
+#include "auc_delong.hip"
 #include "threshold_metrics.hip"
 #include "isotonic.hip"
 #include "gauc.hip"
@@ -316,6 +317,42 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
               "auc");
       },
       py::arg("scores"), py::arg("labels"), py::arg("weights"), py::arg("n"), py::arg("out"), py::arg("ws"),
+      py::arg("ws_bytes"), py::arg("stream"));
+
+  m.def(
+      "delong_workspace_bytes",
+      [](long long n, bool two_models) {
+        const size_t b = fm::delong_workspace_bytes(n, two_models);
+        if (!b) throw std::invalid_argument("auc_delong: n must be in [0, 2^30)");
+        return b;
+      },
+      py::arg("n"), py::arg("two_models"));
+  m.def(
+      "auc_delong",  // DeLong record (hip/auc_delong.hip: 20 int64 words) of one model (scores_b == 0) or two into
+                     // out; asynchronous (ops/kernels.py DelongStats)
+      [](u64 scores_a, u64 scores_b, u64 labels, int n, u64 out, u64 ws, size_t ws_bytes, u64 stream) {
+        check(fm::launch_delong(P<const float>(scores_a), P<const float>(scores_b), P<const float>(labels), n,
+                                P<void>(out), P<void>(ws), ws_bytes, S(stream)),
+              "auc_delong");
+      },
+      py::arg("scores_a"), py::arg("scores_b"), py::arg("labels"), py::arg("n"), py::arg("out"), py::arg("ws"),
+      py::arg("ws_bytes"), py::arg("stream"));
+  m.def(
+      "delong_moments_workspace_bytes",
+      [](long long n) {
+        const size_t b = fm::delong_moments_workspace_bytes(n);
+        if (!b) throw std::invalid_argument("delong_moments: n must be in [0, 2^30)");
+        return b;
+      },
+      py::arg("n"));
+  m.def(
+      "delong_moments",  // the 12 moment words of placements pl_a, pl_b (0: one model) into out; asynchronous
+      [](u64 pl_a, u64 pl_b, u64 labels, int n, u64 out, u64 ws, size_t ws_bytes, u64 stream) {
+        check(fm::launch_delong_moments(P<const uint32_t>(pl_a), P<const uint32_t>(pl_b), P<const float>(labels), n,
+                                        P<void>(out), P<void>(ws), ws_bytes, S(stream)),
+              "delong_moments");
+      },
+      py::arg("pl_a"), py::arg("pl_b"), py::arg("labels"), py::arg("n"), py::arg("out"), py::arg("ws"),
       py::arg("ws_bytes"), py::arg("stream"));
 
   m.def(

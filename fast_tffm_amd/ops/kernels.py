@@ -13,9 +13,12 @@ linear weights ``w`` are a separate fp32 vector (or column ``Kp`` of a packed
 
 from __future__ import annotations
 
+import math
 import os
+import statistics
 import struct
 from dataclasses import dataclass
+from fractions import Fraction
 
 import torch
 
@@ -978,6 +981,182 @@ def auc(scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None
     _check(ws is None, "auc: the workspace is a GPU argument")
     native.cpu().auc(n=n, scores=_p(scores), labels=_p(labels), weights=_p(weights), out=_p(rec))
     return AucStats(rec, weighted, n)
+
+
+# ---------------------------------------------------------------------------
+# AUC confidence intervals and paired model comparison (DeLong)
+# ---------------------------------------------------------------------------
+_DELONG_WORDS = 20    # csrc/hip/auc_delong.hip: kDelongRecWords
+_DELONG_MOMENTS = ("m_pos_aa", "m_neg_aa", "m_pos_bb", "m_neg_bb", "m_pos_ab", "m_neg_ab")  # words 4.., (hi, lo) each
+
+
+class DelongStats(_SortedScoreRecord):
+    """The record of one ``auc_delong`` call, on the op's device: 20 int64 words ``[U2_a, U2_b, P, N, (hi, lo) of
+    M_pos(a,a), M_neg(a,a), M_pos(b,b), M_neg(b,b), M_pos(a,b), M_neg(a,b), NaN scores of a, of b, has_b, sort error
+    word]``; a second moment is ``(hi << 32) + lo``.  The readers synchronise with the launch chain on the GPU,
+    raise when the GPU sort reported a failed look-back, finish the arithmetic in Python integers and fractions
+    and convert to float once at the end: a GPU record and a CPU record give identical floats.  Values that are
+    undefined (a NaN score in either model, an empty class; for the variances a class of one) are NaN."""
+
+    __slots__ = ()
+    _op, _result = "auc_delong", "DeLong statistics"
+
+    def stats(self) -> dict:
+        """The exact Python ints: ``U2_a``, ``U2_b``, ``P``, ``N``, the six second moments ``m_pos_aa`` ...
+        ``m_neg_ab``, ``nans_a``, ``nans_b`` and ``has_b``."""
+        w = [int(x) for x in self._host_rec().tolist()]
+        st = {"U2_a": w[0], "U2_b": w[1], "P": w[2], "N": w[3], "nans_a": w[16], "nans_b": w[17], "has_b": w[18]}
+        for i, name in enumerate(_DELONG_MOMENTS):
+            st[name] = (w[4 + 2 * i] << 32) + w[5 + 2 * i]
+        return st
+
+    def _stats_for(self, other: bool) -> dict:
+        st = self.stats()
+        if other and not st["has_b"]:
+            raise ValueError("auc_delong: the call had no other model")
+        return st
+
+    @staticmethod
+    def _theta(st: dict, m: str):
+        """The AUC of model ``m`` as a Fraction, or None where it is undefined."""
+        if st["nans_a"] or st["nans_b"] or st["P"] < 1 or st["N"] < 1:
+            return None
+        return Fraction(st["U2_" + m], 2 * st["P"] * st["N"])
+
+    @staticmethod
+    def _cov(st: dict, x: str, y: str):
+        """cov(theta_x, theta_y) as a Fraction, or None where it is undefined."""
+        P, N = st["P"], st["N"]
+        if st["nans_a"] or st["nans_b"] or P < 2 or N < 2:
+            return None
+        uu = st["U2_" + x] * st["U2_" + y]
+        s10 = Fraction(st["m_pos_" + x + y] * P - uu, 4 * N * N * P * (P - 1))
+        s01 = Fraction(st["m_neg_" + x + y] * N - uu, 4 * P * P * N * (N - 1))
+        return s10 / P + s01 / N
+
+    def auc(self) -> float:
+        """U2_a / (2 P N), the value ``auc`` returns."""
+        t = self._theta(self.stats(), "a")
+        return _NAN if t is None else float(t)
+
+    def auc_other(self) -> float:
+        """The other model's AUC."""
+        t = self._theta(self._stats_for(True), "b")
+        return _NAN if t is None else float(t)
+
+    def variance(self) -> float:
+        """DeLong's variance of the AUC: S10 / P + S01 / N."""
+        v = self._cov(self.stats(), "a", "a")
+        return _NAN if v is None else float(v)
+
+    def std_error(self) -> float:
+        v = self.variance()
+        return _NAN if v != v else math.sqrt(v)
+
+    def interval(self, level: float = 0.95) -> tuple:
+        """(lo, hi) = AUC -+ z se clipped to [0, 1], z the normal quantile of (1 + level) / 2."""
+        _check(isinstance(level, (int, float)) and 0.0 < level < 1.0, "auc_delong: the level must be in (0, 1)")
+        a, se = self.auc(), self.std_error()
+        if a != a or se != se:
+            return _NAN, _NAN
+        z = statistics.NormalDist().inv_cdf((1 + level) / 2)
+        return max(0.0, a - z * se), min(1.0, a + z * se)
+
+    def covariance(self) -> float:
+        """DeLong's covariance of the two models' AUCs."""
+        v = self._cov(self._stats_for(True), "a", "b")
+        return _NAN if v is None else float(v)
+
+    def difference(self) -> tuple:
+        """(AUC - other's AUC, its standard error, z, two-sided p) of the paired comparison: var = var_a + var_b -
+        2 cov, z = diff / se, p = erfc(|z| / sqrt 2).  Without variance: z 0 and p 1 for equal AUCs, else z +-inf
+        and p 0."""
+        st = self._stats_for(True)
+        ta, tb = self._theta(st, "a"), self._theta(st, "b")
+        if ta is None:
+            return _NAN, _NAN, _NAN, _NAN
+        diff = ta - tb
+        va = self._cov(st, "a", "a")
+        if va is None:
+            return float(diff), _NAN, _NAN, _NAN
+        var = va + self._cov(st, "b", "b") - 2 * self._cov(st, "a", "b")
+        se = math.sqrt(float(var)) if var > 0 else 0.0
+        if var > 0 and se > 0.0:
+            z = float(diff) / se
+        else:
+            z = 0.0 if diff == 0 else math.copysign(math.inf, diff)
+        return float(diff), se, z, math.erfc(abs(z) / math.sqrt(2.0))
+
+
+def delong_workspace(n: int, device: torch.device, two_models: bool = True) -> torch.Tensor:
+    """Device scratch of ``auc_delong`` for up to ``n`` scores of one or (also) two models (GPU)."""
+    return torch.empty(int(native.hip().delong_workspace_bytes(int(n), bool(two_models))), dtype=torch.uint8,
+                       device=device)
+
+
+def auc_delong(scores: torch.Tensor, labels: torch.Tensor, other: torch.Tensor | None = None, *,
+               ws: torch.Tensor | None = None) -> DelongStats:
+    """DeLong, DeLong & Clarke-Pearson (1988) statistics of raw scores: the variance of the ROC AUC and, with the
+    scores ``other`` of a second model on the same examples in the same order, the covariance of the two AUCs --
+    a confidence interval and a paired test without resampling.
+
+    With ``auc``'s conventions (positive iff ``label > 0``, scores compare as IEEE fp32 values, -0.0 == +0.0, NaN
+    scores are counted per model and make every value NaN) a positive's placement is a_i = Nlt(s_i) + Nle(s_i)
+    (the negatives below plus the negatives not above) and a negative's b_j = Pgt(s_j) + Pge(s_j); U2 = sum of the
+    a_i = sum of the b_j, AUC = U2 / (2 P N), and with M_pos(x, y) / M_neg(x, y) the sums of the products of the
+    positives' / negatives' placements under models x and y
+        S10 = (M_pos P - U2_x U2_y) / (4 N^2 P (P - 1)),  S01 = (M_neg N - U2_x U2_y) / (4 P^2 N (N - 1)),
+        cov(x, y) = S10 / P + S01 / N,  var(x) = cov(x, x).
+    Every statistic is an integer (the same on GPU and CPU, whatever the order of the sums).  There are no
+    ``weights``: the variance of a weighted AUC depends on what the weights mean (frequencies, costs, sampling
+    rates), and ``evaluate``, the user of this op, has none.  GPU: hip/auc_delong.hip on the current stream
+    (``ws``: reusable ``delong_workspace``; graph capture as for ``auc``); CPU: a sort per model and two passes.
+    ``n == 0`` launches nothing.
+    """
+    dev, n, _, rdt = _sorted_score_inputs("auc_delong", scores, labels, None)
+    if other is not None:
+        _check(other.device == dev, "auc_delong: other must be on the scores' device")
+        _chk_vec(other, torch.float32, n, "other", dev)
+        _check(other.numel() == n, "auc_delong: one score of the other model per score")
+    if n == 0:
+        rec = torch.zeros(_DELONG_WORDS, dtype=rdt)  # (a host record: nothing is launched)
+        rec[18] = int(other is not None)
+        return DelongStats(rec, False, 0)
+    rec = torch.empty(_DELONG_WORDS, dtype=rdt, device=dev)
+    if _is_gpu(scores):
+        h = native.hip()
+        _, done = _sorted_score_launch(
+            "auc_delong", dev, int(h.delong_workspace_bytes(n, other is not None)), ws, lambda w: h.auc_delong(
+                scores_a=_p(scores), scores_b=_p(other), labels=_p(labels), n=n, out=_p(rec), ws=_p(w),
+                ws_bytes=w.numel(), stream=_stream(scores)))
+        return DelongStats(rec, False, n, done)
+    _check(ws is None, "auc_delong: the workspace is a GPU argument")
+    native.cpu().auc_delong(n=n, scores_a=_p(scores), scores_b=_p(other), labels=_p(labels), out=_p(rec))
+    return DelongStats(rec, False, n)
+
+
+def placement_moments(pl_a: torch.Tensor, pl_b: torch.Tensor | None, labels: torch.Tensor) -> torch.Tensor:
+    """The moments step of ``auc_delong`` on its own: the 12 int64 words (hi, lo) of M_pos(a,a), M_neg(a,a),
+    M_pos(b,b), M_neg(b,b), M_pos(a,b), M_neg(a,b) of placements given as int32 vectors (read as uint32; ``pl_b``
+    None: the (a,a) words, the rest 0), on the placements' device.  Every product t adds ``t >> 32`` to its hi
+    word and ``t & 0xffffffff`` to its lo word."""
+    dev, n = pl_a.device, pl_a.numel()
+    _chk_vec(pl_a, torch.int32, n, "pl_a", dev)
+    _chk_vec(pl_b, torch.int32, n, "pl_b", dev)
+    _chk_vec(labels, torch.float32, n, "labels", dev)
+    _check(labels.numel() == n and (pl_b is None or pl_b.numel() == n), "placement_moments: one label per placement")
+    _check(n < 2**30, "placement_moments: n must be < 2^30")
+    if n == 0:
+        return torch.zeros(12, dtype=torch.int64, device=dev)
+    out = torch.empty(12, dtype=torch.int64, device=dev)
+    if _is_gpu(pl_a):
+        h = native.hip()
+        ws = torch.empty(int(h.delong_moments_workspace_bytes(n)), dtype=torch.uint8, device=dev)
+        h.delong_moments(pl_a=_p(pl_a), pl_b=_p(pl_b), labels=_p(labels), n=n, out=_p(out), ws=_p(ws),
+                         ws_bytes=ws.numel(), stream=_stream(pl_a))
+    else:
+        native.cpu().delong_moments(n=n, pl_a=_p(pl_a), pl_b=_p(pl_b), labels=_p(labels), out=_p(out))
+    return out
 
 
 # ---------------------------------------------------------------------------

@@ -18,6 +18,8 @@ Reference behaviour kept (run_tffm.py:10-90, :213-231):
 * evaluate (new): loss, ROC AUC and -- with ``predict_group_files`` -- grouped AUC of a checkpoint on the
   labelled predict files, and ``<predict_file>_gauc`` with one line per group; with ``threshold_metrics`` or
   targets also average precision, KS, best F1, the targets' operating points and ``<predict_file>_thresholds``;
+  with ``auc_interval`` DeLong's standard error and confidence interval of the AUC, with ``baseline_score_files``
+  DeLong's paired test against another model's scores;
 * calibrate (new): an exact isotonic fit of the checkpoint's scores on the validation files, written as
   ``calibration.json`` into the checkpoint's directory; ``predict --calibrated`` then also writes
   ``<predict_file>_prob`` with one calibrated probability per line.
@@ -43,7 +45,7 @@ from .data.reader import NativeTextReader, Prefetcher, ReaderState, TextBatchRea
 from .models.fm import FactorizationMachine
 from .data.groups import load_group_files
 from .calibration import FILE_NAME as CALIBRATION_FILE, CalibrationError, Calibrator, log_loss_sum_of_blocks
-from .ops.kernels import auc, check_device_errors, gauc, isotonic_fit, rank_metrics, threshold_metrics
+from .ops.kernels import auc, auc_delong, check_device_errors, gauc, isotonic_fit, rank_metrics, threshold_metrics
 from .parallel.dist import DistContext, gather_dealt
 from .utils import checkpoint as ckpt
 from .utils.metrics import MetricsLogger
@@ -196,7 +198,7 @@ class Trainer:
         return loss, v_auc
 
     def validation_report(self, vb, want_auc: bool = True, groups=None, *, rank_cutoffs=None,
-                          want_gauc: bool = True, thresholds=None) -> tuple:
+                          want_gauc: bool = True, thresholds=None, delong=None) -> tuple:
         """(loss, ROC AUC or None, ``GaucStats`` or None) of a labelled batch from ONE forward.  ``groups``:
         ``(this rank's int32 group ids of vb's examples, number of groups)`` for the grouped AUC
         (ops/kernels.py ``gauc``) of the same scores.  Multi-rank: the ids travel with the scores, labels
@@ -205,7 +207,9 @@ class Trainer:
         ``rank_metrics`` on the same gathered scores (no example weights enter it); ``want_gauc`` False leaves
         the third entry None.  With ``thresholds`` = ``(precision targets, recall targets)`` the tuple gains
         a last entry, the ``ThresholdStats`` of ``threshold_metrics`` on the same gathered scores, labels and
-        weights."""
+        weights.  With ``delong`` = ``(every example's baseline score in file order, or None,)`` one more entry
+        follows, the ``DelongStats`` of ``auc_delong`` on the same gathered scores and labels (unweighted: the
+        caller's weights are all ones)."""
         fo = self.model.forward(vb, loss=self.cfg.loss_type)
         loss = self._global_loss(float(fo.loss_sum), vb.B)
 
@@ -214,6 +218,9 @@ class Trainer:
                 return ()
             return (threshold_metrics(scores, labels, weights, precision_targets=thresholds[0],
                                       recall_targets=thresholds[1]),)
+
+        def dlg(scores, labels) -> tuple:
+            return () if delong is None else (auc_delong(scores, labels, delong[0]),)
 
         if rank_cutoffs is not None:
             if groups is None:
@@ -224,15 +231,16 @@ class Trainer:
             ids = ids.view(torch.int32)
             return (loss, auc(scores, labels, weights).value() if want_auc else None,
                     gauc(scores, labels, ids, groups[1], weights) if want_gauc else None,
-                    rank_metrics(scores, labels, ids, groups[1], rank_cutoffs)) + thr(scores, labels, weights)
-        if not want_auc and groups is None and thresholds is None:
+                    rank_metrics(scores, labels, ids, groups[1], rank_cutoffs)) + thr(scores, labels, weights) \
+                + dlg(scores, labels)
+        if not want_auc and groups is None and thresholds is None and delong is None:
             return loss, None, None
         ids = None if groups is None else groups[0].view(torch.float32)
         scores, labels, weights, ids = gather_dealt(self.ctx if self.world > 1 else None,
                                                     [fo.pred[:vb.B].contiguous(), vb.labels, vb.weights, ids])
         v_auc = auc(scores, labels, weights).value() if want_auc else None
         st = None if groups is None else gauc(scores, labels, ids.view(torch.int32), groups[1], weights)
-        return (loss, v_auc, st) + thr(scores, labels, weights)
+        return (loss, v_auc, st) + thr(scores, labels, weights) + dlg(scores, labels)
 
     # ------------------------------------------------------------------
     def train(self) -> dict:
@@ -515,6 +523,11 @@ class Trainer:
         ``nan``.  With ``[Predict] threshold_metrics`` (or targets) the line ends with `` ap A ks K best_f1 F``,
         then `` recall@p<pi> R`` per precision target and `` precision@r<rho> Q`` per recall target
         (ops/kernels.py ``threshold_metrics``), and ``<file>_thresholds`` gets one line per operating point.
+        With ``[Predict] auc_interval = L`` the line then goes on `` auc_se S auc_lo A auc_hi B``: DeLong's
+        standard error of the AUC and the interval at level L (ops/kernels.py ``auc_delong``); with ``[Predict]
+        baseline_score_files`` (one raw score per line, as ``predict`` writes them) it ends with `` baseline_auc A
+        auc_diff D diff_se S z Z p P``: the baseline's AUC on the same examples, this model's AUC minus it, and
+        DeLong's paired test of the difference.
         Returns the metrics per file.
         Multi-rank runs deal the examples as ``predict`` does; rank 0 writes."""
         c = self.cfg
@@ -538,13 +551,24 @@ class Trainer:
             groups = None if ids is None else (ids.to(self.device), gi.num_groups)
             rst = None
             want_thr = (tuple(c.precision_targets), tuple(c.recall_targets)) if c.threshold_metrics else None
+            want_dl = None
+            if c.auc_interval is not None or c.baseline_score_files:
+                base = None
+                if c.baseline_score_files:  # (every rank reads the whole file: the scores are gathered on each)
+                    base = _read_scores(c.baseline_score_files[k])
+                    if base.size != b.B:
+                        raise ValueError(f"{c.baseline_score_files[k]}: {base.size} lines but {path} has {b.B} "
+                                         "examples")
+                    base = torch.from_numpy(base).to(self.device)
+                want_dl = (base,)
             if c.rank_cutoffs:
                 loss, v_auc, st, rst, *tst = self.validation_report(mine.to(self.device), True, groups,
                                                                     rank_cutoffs=tuple(c.rank_cutoffs),
-                                                                    thresholds=want_thr)
+                                                                    thresholds=want_thr, delong=want_dl)
             else:
                 loss, v_auc, st, *tst = self.validation_report(mine.to(self.device), True, groups,
-                                                               thresholds=want_thr)
+                                                               thresholds=want_thr, delong=want_dl)
+            dst = tst.pop() if want_dl is not None else None
             res = {"examples": b.B, "loss": loss, "auc": v_auc}
             line = "evaluate %s: examples %d loss %.8f auc %.8f" % (path, b.B, loss, v_auc)
             if st is not None:
@@ -577,6 +601,15 @@ class Trainer:
                     line += " precision@r%g %.8f" % (t, res["precision@r%g" % t])
                 if self.rank == 0:
                     res["thresholds_file"] = _write_thresholds(path + "_thresholds", ts)
+            if dst is not None and c.auc_interval is not None:
+                lo, hi = dst.interval(c.auc_interval)
+                res.update(auc_se=dst.std_error(), auc_lo=lo, auc_hi=hi)
+                line += " auc_se %.8f auc_lo %.8f auc_hi %.8f" % (res["auc_se"], lo, hi)
+            if dst is not None and c.baseline_score_files:
+                diff, se, z, p = dst.difference()
+                res.update(baseline_auc=dst.auc_other(), auc_diff=diff, diff_se=se, z=z, p=p)
+                line += " baseline_auc %.8f auc_diff %.8f diff_se %.8f z %.4f p %.6g" % (res["baseline_auc"], diff,
+                                                                                         se, z, p)
             self.print(line)
             results[path] = res
         return results
@@ -721,6 +754,13 @@ def _write_group_aucs(out: str, gi, recs: list) -> str:
             f.write("%s %s %s %s %d\n" % (key, "nan" if invalid else str(np.float32(a)), recs[g][1], recs[g][2],
                                           sizes[g]))
     return out
+
+
+def _read_scores(path: str) -> np.ndarray:
+    """The fp32 scores of a ``<file>_score`` file, one per line: what ``predict`` wrote, bit for bit (it prints
+    the shortest decimal that reads back as the same fp32 value)."""
+    with open(path) as f:
+        return np.array([float(t) for t in f.read().split()], dtype=np.float64).astype(np.float32)
 
 
 def _write_thresholds(out: str, ts) -> str:
