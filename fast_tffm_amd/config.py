@@ -38,6 +38,10 @@ Extensions (new keys, all optional):
                 validation_ap = true|false (average precision of the validation scores, weighted like the loss,
                                 printed and logged after those lines; default false), ap_tolerance = <float>
                                 (stop when it is >= this; needs validation_ap and validation_files),
+                loss_type = mse|logistic|rank_softmax (rank_softmax: the listwise loss, a softmax cross-entropy
+                                per group over the examples of one batch; local mode, one rank),
+                rank_group_feature = <P> (rank_softmax only: an example's group key is the table row of its P-th
+                                feature, 0-based; default 0; examples with fewer features are left out),
                 checkpoint_format = dense|sparse (sparse: a checkpoint stores only the rows that differ from
                                 their counter-based init, and restore regenerates the others; default dense)
   [Predict]     predict_group_files = <files> (one group key per line, parallel to predict_files: the
@@ -113,7 +117,8 @@ class FMRunConfig:
     num_epochs: int = 10
     learning_rate: float = 0.01
     adagrad_init_accumulator: float = 0.1
-    loss_type: str = "mse"
+    loss_type: str = "mse"      # mse | logistic | rank_softmax (listwise, per group of one batch)
+    rank_group_feature: int = 0  # rank_softmax: the feature position whose table row is the group key
     save_steps: int = 100
     queue_size: int = 10000
     shuffle_threads: int = 1
@@ -181,6 +186,7 @@ class FMRunConfig:
         else:
             opt = OptConfig(self.optimizer, lr=self.learning_rate, initial_accumulator=self.adagrad_init_accumulator)
         return FMConfig(vocabulary_size=self.vocabulary_size, factor_num=self.factor_num, loss_type=self.loss_type,
+                        rank_group_feature=self.rank_group_feature,
                         factor_lambda=self.factor_lambda, bias_lambda=self.bias_lambda, batch_size=self.batch_size,
                         init_value_range=self.init_value_range, seed=self.seed,
                         dtype={"fp32": torch.float32, "bf16": torch.bfloat16,
@@ -296,8 +302,18 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
     if c.checkpoint_format not in ("dense", "sparse"):
         raise ConfigError(f"[Train] checkpoint_format must be dense or sparse, got {c.checkpoint_format}")
 
-    if c.loss_type not in ("logistic", "mse"):
-        raise ConfigError("loss_type must be 'logistic' or 'mse', got %r" % c.loss_type)
+    if c.loss_type not in ("logistic", "mse", "rank_softmax"):
+        raise ConfigError("loss_type must be 'logistic', 'mse' or 'rank_softmax', got %r" % c.loss_type)
+    rgf = read(TRAIN, "rank_group_feature", required=False)
+    if rgf is not None:
+        if c.loss_type != "rank_softmax":
+            raise ConfigError("rank_group_feature needs loss_type = rank_softmax.")
+        try:
+            c.rank_group_feature = int(rgf)
+        except ValueError:
+            c.rank_group_feature = -1
+        if c.rank_group_feature < 0:
+            raise ConfigError("rank_group_feature must be an integer >= 0, got %s." % rgf.strip())
     if c.optimizer not in ("adagrad", "ftrl", "sgd"):
         raise ConfigError("optimizer must be adagrad|ftrl|sgd, got %r" % c.optimizer)
     if c.dtype not in _TABLE_DTYPES:
@@ -387,6 +403,9 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
     c.prefetch_rows = opt(DISTRIBUTED, "prefetch_rows", lambda s: s.strip().lower(), c.prefetch_rows)
     c.overlap_grads = opt(DISTRIBUTED, "overlap_grads", lambda s: s.strip().lower(), c.overlap_grads)
     c.staleness = opt(DISTRIBUTED, "staleness", int, c.staleness)
+    if c.loss_type == "rank_softmax" and c.mode not in ("auto", "local"):
+        raise ConfigError("loss_type = rank_softmax needs [Distributed] mode = local (or auto on one rank), got %s"
+                          % c.mode)
     if c.comm_dtype not in ("auto", "storage", "fp32", "bf16"):
         raise ConfigError(f"[Distributed] comm_dtype must be auto, fp32 or bf16, got {c.comm_dtype}")
     if c.staleness not in (0, 1):

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <limits>
 #include <numeric>
 #include <type_traits>
 #include <vector>
@@ -647,6 +648,68 @@ bool rank_metrics(int n, long long G, const float* scores, const float* labels, 
   std::memcpy(o + 16, &nans, 8);
   std::memcpy(o + 24, &zero, 8);
   return true;
+}
+
+void group_keys(int B, const int* offsets, const int* rows, int pos, int num_rows, int* keys) {
+  for (int i = 0; i < B; ++i) {
+    int k = -1;
+    if (offsets[i] >= 0 && offsets[i + 1] - offsets[i] > pos) {
+      const int r = rows[offsets[i] + pos];
+      if (static_cast<unsigned>(r) < static_cast<unsigned>(num_rows)) k = r;
+    }
+    keys[i] = k;
+  }
+}
+
+void group_plan(int n, const int* ids, int key_bits, int* sidx, int* first, int* end) {
+  const uint32_t excl = (1u << key_bits) - 1u;
+  std::vector<uint32_t> key(n > 0 ? n : 0);
+  for (int e = 0; e < n; ++e)
+    key[e] = (ids[e] < 0 || static_cast<uint32_t>(ids[e]) >= excl) ? excl : static_cast<uint32_t>(ids[e]);
+  std::iota(sidx, sidx + n, 0);
+  std::stable_sort(sidx, sidx + n, [&key](int a, int b) { return key[a] < key[b]; });
+  for (int j = 0; j < n;) {
+    const uint32_t k = key[sidx[j]];
+    int e = j + 1;
+    while (e < n && key[sidx[e]] == k) ++e;
+    for (int q = j; q < e; ++q) {
+      first[q] = k == excl ? q : j;
+      end[q] = k == excl ? 0 : e;
+    }
+    j = e;
+  }
+}
+
+double group_softmax(int n, const int* sidx, const int* first, const int* end, const float* scores,
+                     const float* labels, const float* weights, double grad_scale, float* dpred) {
+  double loss = 0.0;
+  auto gain = [labels, weights](int ex) {
+    return (weights ? static_cast<double>(weights[ex]) : 1.0) * (labels[ex] > 0.f ? static_cast<double>(labels[ex]) : 0.0);
+  };
+  for (int j = 0; j < n;) {
+    if (end[j] == 0) {
+      dpred[sidx[j]] = 0.f;
+      ++j;
+      continue;
+    }
+    const int e = end[j];
+    double m = -std::numeric_limits<double>::infinity(), Z = 0.0, A = 0.0, T = 0.0;
+    for (int q = j; q < e; ++q) m = std::fmax(m, static_cast<double>(scores[sidx[q]]));
+    for (int q = j; q < e; ++q) {
+      const double s = scores[sidx[q]], a = gain(sidx[q]);
+      Z += std::exp(s - m);
+      A += a;
+      T += a * s;
+    }
+    for (int q = j; q < e; ++q) {
+      const double s = scores[sidx[q]];
+      const double d = A != 0.0 ? A * (std::exp(s - m) / Z) - gain(sidx[q]) : 0.0;
+      dpred[sidx[q]] = static_cast<float>(grad_scale * d);
+    }
+    if (A != 0.0) loss += A * (m + std::log(Z)) - T;
+    j = e;
+  }
+  return loss;
 }
 
 namespace {

@@ -89,6 +89,17 @@ void gauc(int n, long long G, const float* scores, const float* labels, const fl
 bool rank_metrics(int n, long long G, const float* scores, const float* labels, const int* groups, const int* k,
                   int nk, void* out, double* per);
 
+// Listwise ranking loss (hip/group_loss.hip: same definition, fp64, a plain sort and loop).
+// group_keys: keys[i] = rows[offsets[i] + pos], -1 (excluded) for an example with fewer features or a row outside
+// [0, num_rows).  group_plan: sidx[n] = the examples in (group, batch) order (ids < 0 or >= 2^key_bits - 1 are
+// excluded and come last), first[n] / end[n] = every sorted position's group range (end == 0: excluded).
+// group_softmax: dpred[n] (example order) = fp32(grad_scale (A_g softmax_g(s)_i - a_i)) with a_i = w_i max(y_i, 0);
+// returns sum_g A_g (m_g + log Z_g) - T_g; a group with A_g == 0 and an excluded example add exactly 0.
+void group_keys(int B, const int* offsets, const int* rows, int pos, int num_rows, int* keys);
+void group_plan(int n, const int* ids, int key_bits, int* sidx, int* first, int* end);
+double group_softmax(int n, const int* sidx, const int* first, const int* end, const float* scores,
+                     const float* labels, const float* weights, double grad_scale, float* dpred);
+
 // Exact isotonic regression (hip/isotonic.hip: same definition, same two modes) of n >= 1 scores, weights null
 // or all > 0: the blocks' first / last score lo, hi, weight W, positive weight Y (uint64 when weights is null,
 // else fp64 summed in sorted order) and value v = Y / W (fp64), [n] each; out[5] = blocks, total weight, positive

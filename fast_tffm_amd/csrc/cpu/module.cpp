@@ -530,6 +530,32 @@ PYBIND11_MODULE(_fm_cpu, m) {
       [](u64 out) { fm::rank_dcg_table(P<double>(out)); }, py::arg("out"));
 
   m.def(
+      "group_keys",
+      [](int B, u64 offsets, u64 rows, int pos, int num_rows, u64 keys) {
+        if (B < 0 || pos < 0 || num_rows < 1) throw std::invalid_argument("group_keys: B >= 0, pos >= 0, num_rows >= 1");
+        fm::cpu::group_keys(B, P<const int>(offsets), P<const int>(rows), pos, num_rows, P<int>(keys));
+      },
+      py::arg("B"), py::arg("offsets"), py::arg("rows"), py::arg("pos"), py::arg("num_rows"), py::arg("keys"));
+  m.def(
+      "group_plan",
+      [](int n, u64 ids, int key_bits, u64 sidx, u64 first, u64 end) {
+        if (n < 0 || key_bits < 1 || key_bits > 31) throw std::invalid_argument("group_plan: key_bits must be in [1, 31]");
+        py::gil_scoped_release nogil;
+        fm::cpu::group_plan(n, P<const int>(ids), key_bits, P<int>(sidx), P<int>(first), P<int>(end));
+      },
+      py::arg("n"), py::arg("ids"), py::arg("key_bits"), py::arg("sidx"), py::arg("first"), py::arg("end"));
+  m.def(
+      "group_softmax",
+      [](int n, u64 sidx, u64 first, u64 end, u64 scores, u64 labels, u64 weights, double grad_scale, u64 dpred) {
+        py::gil_scoped_release nogil;
+        return fm::cpu::group_softmax(n, P<const int>(sidx), P<const int>(first), P<const int>(end),
+                                      P<const float>(scores), P<const float>(labels), P<const float>(weights),
+                                      grad_scale, P<float>(dpred));
+      },
+      py::arg("n"), py::arg("sidx"), py::arg("first"), py::arg("end"), py::arg("scores"), py::arg("labels"),
+      py::arg("weights"), py::arg("grad_scale"), py::arg("dpred"));
+
+  m.def(
       "isotonic",
       [](int n, u64 scores, u64 labels, u64 weights, u64 lo, u64 hi, u64 W, u64 Y, u64 v, u64 fitted, u64 out,
          int tile) {

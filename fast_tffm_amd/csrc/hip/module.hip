@@ -33,6 +33,7 @@ using u64 = std::uintptr_t;
 #include "isotonic.hip"
 #include "gauc.hip"
 #include "rank_metrics.hip"
+#include "group_loss.hip"
 #include "shard.hip"
 #include "init.hip"
 #include "ckpt.hip"
@@ -463,6 +464,51 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       },
       py::arg("scores"), py::arg("labels"), py::arg("groups"), py::arg("n"), py::arg("G"), py::arg("cutoffs"),
       py::arg("out"), py::arg("per"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
+
+  m.attr("GROUP_LOSS_TILE") = fm::kGlTile;
+  m.def(
+      "group_loss_workspace_bytes",
+      [](long long n) {
+        const size_t b = fm::group_loss_workspace_bytes(n);
+        if (!b) throw std::invalid_argument("group loss: n must be in [0, 2^30)");
+        return b;
+      },
+      py::arg("n"));
+  m.def(
+      "group_plan_offsets",  // byte offsets of (sorted idx, first, end, error word) in a workspace for n examples
+      [](int n) {
+        size_t off[4];
+        fm::group_plan_offsets(n, off);
+        return std::vector<size_t>(off, off + 4);
+      },
+      py::arg("n"));
+  m.def(
+      "group_keys",  // keys[i] = rows[offsets[i] + pos], -1 for an example with fewer features; asynchronous
+      [](int B, u64 offsets, u64 rows, int pos, int num_rows, u64 keys, u64 stream) {
+        check(fm::launch_group_keys(B, P<const int>(offsets), P<const int>(rows), pos, num_rows, P<int>(keys),
+                                    S(stream)), "group_keys");
+      },
+      py::arg("B"), py::arg("offsets"), py::arg("rows"), py::arg("pos"), py::arg("num_rows"), py::arg("keys"),
+      py::arg("stream"));
+  m.def(
+      "group_plan",  // the batch half of the listwise loss: group-sorted example order and group ranges into ws
+      [](u64 ids, int n, int key_bits, u64 ws, size_t ws_bytes, u64 stream) {
+        const int rc = fm::launch_group_plan(P<const int>(ids), n, key_bits, P<void>(ws), ws_bytes, S(stream));
+        if (rc == -8) throw std::invalid_argument("group_plan: key_bits must be in [1, 31]");
+        check(rc, "group_plan");
+      },
+      py::arg("ids"), py::arg("n"), py::arg("key_bits"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
+  m.def(
+      "group_softmax",  // the score half: dpred[n] (example order) and loss[1] (fp32) from a plan; asynchronous
+      [](u64 plan, size_t plan_bytes, int n, u64 scores, u64 labels, u64 weights, double grad_scale, u64 dpred,
+         u64 loss, u64 ws, size_t ws_bytes, u64 stream) {
+        check(fm::launch_group_softmax(P<const void>(plan), plan_bytes, n, P<const float>(scores),
+                                       P<const float>(labels), P<const float>(weights), grad_scale, P<float>(dpred),
+                                       P<float>(loss), P<void>(ws), ws_bytes, S(stream)),
+              "group_softmax");
+      },
+      py::arg("plan"), py::arg("plan_bytes"), py::arg("n"), py::arg("scores"), py::arg("labels"), py::arg("weights"),
+      py::arg("grad_scale"), py::arg("dpred"), py::arg("loss"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
 
   m.def(
       "gather_rows",

@@ -7,6 +7,9 @@ ids -> FmScorer -> loss (mean of weighted logistic/MSE) -> Adagrad.minimize of
 Here the step is an explicit pipeline of native kernels, no autograd graph:
 
   local (world == 1):   fwd+loss (direct table gather) | dedup -> bwd+optimizer
+                        (loss_type = rank_softmax: fwd scores | dedup + group plan -> listwise loss -> bwd;
+                        the plan half of ops.kernels.group_softmax_loss depends on the batch alone and travels
+                        with the batch's dedup, the score half sits between forward and backward)
   shard (row-sharded):  dedup -> a2a(ids) -> owner gather -> a2a(rows) -> fwd
                         -> bwd(emit grads) -> a2a(grads) -> owner sum+optimizer
   dp    (replicated):   local fwd/bwd(emit) -> all_gather(ids, grads) -> every
@@ -58,7 +61,8 @@ def side_stream(device):
 class FMConfig:
     vocabulary_size: int
     factor_num: int
-    loss_type: str = "mse"            # "mse" | "logistic"
+    loss_type: str = "mse"            # "mse" | "logistic" | "rank_softmax" (listwise; local mode, one rank)
+    rank_group_feature: int = 0       # rank_softmax: an example's group key = the table row of this feature position
     factor_lambda: float = 0.0
     bias_lambda: float = 0.0
     batch_size: int = 50000           # configured batch size: reg_score / batch_size (fm_model.py:345-347)
@@ -82,9 +86,11 @@ class FMConfig:
 class _Workspace:
     """Per-step buffers, grown on demand and then reused (no per-step allocation)."""
 
-    def __init__(self, device: torch.device, Kp: int, CH: int, r1_dtype: torch.dtype = torch.float32):
+    def __init__(self, device: torch.device, Kp: int, CH: int, r1_dtype: torch.dtype = torch.float32,
+                 group_loss: bool = False):
         self.device, self.Kp, self.CH, self.r1_dtype = device, Kp, CH, r1_dtype
         self.cap_b = self.cap_n = 0
+        self.group = _GroupBufs() if group_loss else None  # listwise loss only: its plan of the unplanned step
 
     def ensure(self, B: int, nnz: int) -> None:
         dev, Kp = self.device, self.Kp
@@ -94,6 +100,8 @@ class _Workspace:
             self.dpred = torch.empty(cap, dtype=torch.float32, device=dev)
             self.r1 = torch.empty((cap, Kp), dtype=self.r1_dtype, device=dev)
             self.cap_b = cap
+            if self.group is not None:
+                self.group.ensure(cap, dev)
         if nnz > self.cap_n:
             cap = max(nnz, int(self.cap_n * 1.25), 1)
             self.dd = K.DedupWorkspace(cap, dev, self.CH)
@@ -104,13 +112,32 @@ class _Workspace:
         if not hasattr(self, "fwd_partial"):
             self.fwd_partial = torch.zeros(3 * 4096, dtype=torch.float32, device=dev)
 
+class _GroupBufs:
+    """Buffers of one batch's group plan (listwise loss): the examples' group keys and the workspace both halves of
+    ``K.group_softmax_loss`` use.  Allocated by models with ``loss_type = rank_softmax`` only."""
+
+    def __init__(self):
+        self.keys: torch.Tensor | None = None
+        self.ws: torch.Tensor | None = None
+        self.cap = 0
+
+    def ensure(self, B: int, dev) -> None:
+        if self.keys is None or self.cap < B:
+            self.cap = max(B, 1, int(1.25 * self.cap))
+            self.keys = torch.empty(self.cap, dtype=torch.int32, device=dev)
+            self.ws = K.group_loss_workspace(self.cap, dev) if dev.type == "cuda" else None
+
+
 class _LocalSlot:
-    """Double-buffered dedup workspace of the local lookahead pipeline."""
+    """Double-buffered dedup workspace of the local lookahead pipeline (and, for the listwise loss, the batch's
+    group plan: it is recycled with the dedup, under the same ``done`` event)."""
 
     def __init__(self):
         self.dd: K.DedupWorkspace | None = None
         self.rows32: torch.Tensor | None = None
         self.done = None
+        self.group: _GroupBufs | None = None
+        self.gplan: K.GroupPlan | None = None
 
     def ensure(self, nnz: int, dev, CH: int) -> None:
         if self.dd is None or self.dd.cap < nnz:
@@ -126,6 +153,7 @@ class _LocalPlan:
     rows: torch.Tensor
     dd: object
     ready: object
+    gplan: object = None   # K.GroupPlan of the batch (listwise loss), in the slot's buffers
 
 
 class _LookaheadGraphRing:
@@ -171,7 +199,7 @@ class _LookaheadGraphRing:
         nxt = (k + 1) % n
         with torch.cuda.stream(side):
             self.rows[nxt % 2], self.dds[nxt % 2] = m._plan_into(m._lslots[nxt % 2], self.bufs[nxt])
-        out = m._fwd_bwd_local(self.bufs[k], self.rows[k % 2], self.dds[k % 2])
+        out = m._fwd_bwd_local(self.bufs[k], self.rows[k % 2], self.dds[k % 2], m._lslots[k % 2].gplan)
         main.wait_stream(side)
         return out
 
@@ -259,6 +287,14 @@ class FactorizationMachine:
         if mode == "local" and self.world > 1:
             raise ValueError("mode=local needs world_size == 1")
         self.mode = mode
+        self.rank_loss = cfg.loss_type == K.RANK_LOSS
+        if self.rank_loss and (mode != "local" or self.world > 1):
+            raise ValueError(f"loss_type = {K.RANK_LOSS} needs mode = local and world_size == 1 (groups are formed "
+                             f"within one rank's batch), got mode = {mode}, world_size = {self.world}")
+        if not self.rank_loss and cfg.rank_group_feature != 0:
+            raise ValueError(f"rank_group_feature needs loss_type = {K.RANK_LOSS}, got loss_type = {cfg.loss_type}")
+        if cfg.rank_group_feature < 0:
+            raise ValueError(f"rank_group_feature must be >= 0, got {cfg.rank_group_feature}")
         sharded = mode == "shard"
         # (dp_dense: the replica is cut into P blocks of W equal row ranges, one per rank)
         rows_multiple = 1
@@ -272,7 +308,8 @@ class FactorizationMachine:
                              rows_multiple=rows_multiple)
         self.K, self.Kp = self.table.K, self.table.Kp
         self.rps = rows_per_shard(cfg.vocabulary_size, self.world) if sharded else cfg.vocabulary_size
-        self.ws = _Workspace(self.device, self.Kp, cfg.dedup_chunk, K.r1_dtype(cfg.dtype))
+        self.ws = _Workspace(self.device, self.Kp, cfg.dedup_chunk, K.r1_dtype(cfg.dtype),
+                             group_loss=self.rank_loss)
         self.global_step = 0
         self._side = None
         # lookahead dedup plans (eager local path): the current step's plan and up to two pending
@@ -488,12 +525,17 @@ class FactorizationMachine:
                 sb = self._slot_bits(b)
                 dd = K.dedup(rows, ws=ws.dd, key_bits=bits_for(self.table.rows), gen_codes=True, vals=b.vals,
                              num_examples=b.B, Kp=self.Kp, ex_shift=sb, offsets=b.offsets)
+                gplan = self._group_plan(ws.group, b, rows)
         else:
             ex = K.csr_rows(b.offsets, out=ws.dd.ex_of_occ[: b.nnz], nnz=b.nnz)
+            gplan = self._group_plan(ws.group, b, rows)
         with roctx_range("fwd"):
+            # (listwise loss: its score half needs the plan, so the join with the side stream moves up to between
+            # the scores and the loss; the pointwise step joins before the backward, as ever)
             fo = self._train_forward(b, rows, self.table.v, self.table.w, total_B=b.B, defer_loss=gpu,
-                                     max_feats=b.max_feats)
-            self.bias_step(fo.dpred)
+                                     max_feats=b.max_feats, gplan=gplan,
+                                     gplan_ready=(lambda: main.wait_stream(side)) if gpu and self.rank_loss else None)
+            self._bias_step(fo)
         if gpu:
             main.wait_stream(side)
         else:
@@ -501,16 +543,45 @@ class FactorizationMachine:
         self._local_backward(dd, fo)
         return StepOut(fo.finish_loss(), b.B)
 
+    def _bias_step(self, fo: K.FwdOut) -> None:
+        """``bias_step`` of a training forward.  The listwise loss skips it: its gradient sums to zero within every
+        group, so the global bias gets none."""
+        if not self.rank_loss:
+            self.bias_step(fo.dpred)
+
+    def _group_plan(self, bufs: "_GroupBufs | None", b: Batch, rows: torch.Tensor) -> "K.GroupPlan | None":
+        """The batch half of the listwise loss for ``b`` into ``bufs`` on the current stream (None for the
+        pointwise losses: nothing is launched or allocated): every example's group key -- the table row of its
+        ``rank_group_feature``-th feature -- and ``K.group_plan`` over them."""
+        if not self.rank_loss:
+            return None
+        bufs.ensure(b.B, self.device)
+        keys = K.group_keys(b.offsets, rows, self.cfg.rank_group_feature, self.table.rows, out=bufs.keys)
+        return K.group_plan(keys, bits_for(self.table.rows + 1), ws=bufs.ws)
+
     def _train_forward(self, sb: Batch, rows: torch.Tensor, src_v: torch.Tensor, src_w: torch.Tensor, *,
-                       total_B: int, e0: int = 0, **extra) -> K.FwdOut:
+                       total_B: int, e0: int = 0, gplan: "K.GroupPlan | None" = None, gplan_ready=None,
+                       **extra) -> K.FwdOut:
         """The training forward of every executor: scores, loss and dL/dpred of the examples of ``sb`` (a
         batch, or the part of one that starts at example ``e0``) over the rows ``src_v`` / ``src_w`` (the
         table, or gathered wire rows), written into the workspace's ``pred`` / ``r1`` / ``dpred`` at
         ``e0 : e0 + sb.B``.  ``rows``: each occurrence's row in the source.  ``total_B``: the examples of
-        the whole batch (the gradient's 1 / B).  ``extra``: what differs between the executors
-        (``defer_loss``, ``max_feats``, ``self_rows``, ``seg_lookup``), passed on to ``K.fm_forward``."""
+        the whole batch (the gradient's 1 / B).  ``gplan`` (listwise loss): the batch's group plan, and
+        ``gplan_ready``, called between the scores and the loss when the plan is made on another stream.
+        ``extra``: what differs between the executors (``defer_loss``, ``max_feats``, ``self_rows``,
+        ``seg_lookup``), passed on to ``K.fm_forward``."""
         ws, cfg = self.ws, self.cfg
         e1 = e0 + sb.B
+        if self.rank_loss:  # scores only; the listwise loss couples the examples of a group: its own op
+            extra.pop("defer_loss", None)
+            fo = K.fm_forward(sb.offsets, rows, sb.vals, src_v, src_w, self.Kp, loss="none", want_r1=True,
+                              pred=ws.pred[e0:e1], r1=ws.r1[e0:e1], partial=ws.fwd_partial, threads=cfg.threads,
+                              bias=self.gbias, **extra)
+            if gplan_ready is not None:
+                gplan_ready()
+            dpred, loss_sum = K.group_softmax_loss(gplan, fo.pred[: sb.B], sb.labels, sb.weights,
+                                                   self.grad_scale(total_B), dpred=ws.dpred[e0:e1])
+            return K.FwdOut(fo.pred, fo.r1, dpred, loss_sum, None, None)
         return K.fm_forward(sb.offsets, rows, sb.vals, src_v, src_w, self.Kp, labels=sb.labels, weights=sb.weights,
                             loss=cfg.loss_type, grad_scale=self.grad_scale(total_B), want_r1=True,
                             pred=ws.pred[e0:e1], r1=ws.r1[e0:e1], dpred=ws.dpred[e0:e1], partial=ws.fwd_partial,
@@ -553,7 +624,7 @@ class FactorizationMachine:
             rows, dd = self._plan_into(slot, b)
             ev = torch.cuda.Event()
             ev.record(st)
-        return _LocalPlan(b, idx, rows, dd, ev)
+        return _LocalPlan(b, idx, rows, dd, ev, slot.gplan)
 
     def _plan_into(self, slot: "_LocalSlot", b: Batch):
         """dedup of ``b`` (occurrence codes generated inside its sort) into ``slot`` on the current stream;
@@ -565,14 +636,19 @@ class FactorizationMachine:
         kb = bits_for(self.table.rows)
         dd = K.dedup(rows, ws=slot.dd, key_bits=kb, gen_codes=True, vals=b.vals,
                      num_examples=b.B, Kp=self.Kp, ex_shift=sb, offsets=b.offsets)
+        if self.rank_loss:
+            if slot.group is None:
+                slot.group = _GroupBufs()
+            slot.gplan = self._group_plan(slot.group, b, rows)
         return rows, dd
 
-    def _fwd_bwd_local(self, b: Batch, rows: torch.Tensor, dd) -> StepOut:
-        """Forward + loss + backward/update of ``b`` on the current stream (dedup ``dd`` ready)."""
+    def _fwd_bwd_local(self, b: Batch, rows: torch.Tensor, dd, gplan: "K.GroupPlan | None" = None) -> StepOut:
+        """Forward + loss + backward/update of ``b`` on the current stream (dedup ``dd`` ready, and with the
+        listwise loss the group plan ``gplan`` made beside it)."""
         with roctx_range("fwd"):
             fo = self._train_forward(b, rows, self.table.v, self.table.w, total_B=b.B, defer_loss=True,
-                                     max_feats=b.max_feats)
-            self.bias_step(fo.dpred)
+                                     max_feats=b.max_feats, gplan=gplan)
+            self._bias_step(fo)
         self._local_backward(dd, fo)
         return StepOut(fo.finish_loss(), b.B)
 
@@ -619,7 +695,7 @@ class FactorizationMachine:
         nb_ready = self._inputs_ready(next_batch)
         pl = self._take_local_plan(b)
         main.wait_event(pl.ready)
-        out = self._fwd_bwd_local(b, pl.rows, pl.dd)
+        out = self._fwd_bwd_local(b, pl.rows, pl.dd, pl.gplan)
         done = torch.cuda.Event()
         done.record(main)
         self._lslots[pl.slot].done = done
@@ -673,12 +749,22 @@ class FactorizationMachine:
         if self.closed and self.mode != "local":
             raise RuntimeError("forward on a closed multi-rank FactorizationMachine")
         if self.mode == "shard":
+            if loss == K.RANK_LOSS:
+                raise ValueError(f"loss = {K.RANK_LOSS} needs mode = local (groups are formed within one rank's batch)")
             return self._exchange.forward(b, loss=loss, want_reg=want_reg, want_r1=want_r1)
         return self._local_forward(b, loss=loss, want_reg=want_reg, want_r1=want_r1)
 
     def _local_forward(self, b: Batch, *, loss: str, want_reg: bool, want_r1: bool) -> K.FwdOut:
         """``forward`` on this rank's own table: the local model and the replicas of dp / dp_dense."""
         rows = b.ids.to(torch.int32)
+        if loss == K.RANK_LOSS:  # the listwise loss of the batch's groups (the training step's key rule)
+            fo = K.fm_forward(b.offsets, rows, b.vals, self.table.v, self.table.w, self.Kp, loss="none",
+                              want_r1=want_r1, want_reg=want_reg, threads=self.cfg.threads, bias=self.gbias,
+                              max_feats=b.max_feats)
+            keys = K.group_keys(b.offsets, rows, self.cfg.rank_group_feature, self.table.rows)
+            plan = K.group_plan(keys, bits_for(self.table.rows + 1))
+            fo.dpred, fo.loss_sum = K.group_softmax_loss(plan, fo.pred, b.labels, b.weights, 1.0)
+            return fo
         return K.fm_forward(b.offsets, rows, b.vals, self.table.v, self.table.w, self.Kp, labels=b.labels,
                             weights=b.weights, loss=loss, grad_scale=1.0, want_r1=want_r1, want_reg=want_reg,
                             threads=self.cfg.threads, bias=self.gbias, max_feats=b.max_feats)

@@ -1523,6 +1523,138 @@ def rank_metrics(scores: torch.Tensor, labels: torch.Tensor, groups: torch.Tenso
 
 
 # ---------------------------------------------------------------------------
+# listwise ranking loss: softmax cross-entropy per group of one batch
+# ---------------------------------------------------------------------------
+RANK_LOSS = "rank_softmax"  # [Train] loss_type: not one of LOSS_TYPES, the forward kernels do not know it
+
+
+class GroupPlan:
+    """The batch half of the listwise loss (``group_plan``): ``sidx`` the examples in (group, batch) order, the
+    excluded ones last, and ``first`` / ``end``, every sorted position's group range (``end == 0``: excluded) --
+    int32 ``[n]`` each; on the GPU views of ``ws``, the workspace the plan lives in (``err``: the sort's error
+    word there), which must stay untouched until the last ``group_softmax_loss`` that reads the plan has run."""
+
+    __slots__ = ("n", "key_bits", "ws", "sidx", "first", "end", "err")
+
+    def __init__(self, n, key_bits, ws, sidx, first, end, err=None):
+        self.n, self.key_bits, self.ws = n, key_bits, ws
+        self.sidx, self.first, self.end, self.err = sidx, first, end, err
+
+
+def group_loss_tile() -> int:
+    """Sorted positions per workgroup of the GPU op (hip/group_loss.hip kGlTile): where its tests put their sizes."""
+    return int(native.hip().GROUP_LOSS_TILE)
+
+
+def group_loss_workspace(n: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of ``group_plan`` / ``group_softmax_loss`` for up to ``n`` examples (GPU): one workspace
+    serves both halves of one batch."""
+    return torch.empty(int(native.hip().group_loss_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def group_keys(offsets: torch.Tensor, rows: torch.Tensor, pos: int, num_rows: int, *,
+               out: torch.Tensor | None = None) -> torch.Tensor:
+    """Group key of every example of a CSR batch: ``rows[offsets[i] + pos]``, the table row of its ``pos``-th
+    feature (0-based; after hashing or the modulo); -1 -- excluded from the listwise loss -- for an example with
+    fewer than ``pos + 1`` features.  int32 ``[B]``, asynchronous on the current stream."""
+    dev = rows.device
+    B = offsets.numel() - 1
+    _check(B >= 0, "offsets: needs B + 1 entries")
+    _check(isinstance(pos, int) and not isinstance(pos, bool) and pos >= 0,
+           f"group_keys: pos must be an int >= 0, got {pos!r}")
+    _check(1 <= int(num_rows) < 2**31 - 1, "group_keys: num_rows must be in [1, 2^31 - 1)")
+    _chk_vec(offsets, torch.int32, B + 1, "offsets", dev)
+    _chk_vec(rows, torch.int32, None, "rows", dev)
+    if out is None:
+        out = torch.empty(B, dtype=torch.int32, device=dev)
+    _chk_vec(out, torch.int32, B, "out", dev)
+    if B == 0:
+        return out[:0]
+    if _is_gpu(rows):
+        native.hip().group_keys(B=B, offsets=_p(offsets), rows=_p(rows), pos=pos, num_rows=int(num_rows), keys=_p(out),
+                                stream=_stream(rows))
+    else:
+        native.cpu().group_keys(B=B, offsets=_p(offsets), rows=_p(rows), pos=pos, num_rows=int(num_rows), keys=_p(out))
+    return out[:B]
+
+
+def group_plan(keys: torch.Tensor, key_bits: int, *, ws: torch.Tensor | None = None) -> GroupPlan:
+    """Group the examples of one batch by their int32 ``keys``: ids in ``[0, 2^key_bits - 1)``; an id ``< 0`` (or
+    at or above that bound: the sort's all-ones key is theirs) marks an excluded example.  ``key_bits`` in [1, 31]:
+    ``bits_for(num_rows + 1)`` for keys that are table rows.  GPU: hip/group_loss.hip on the current stream into
+    ``ws`` (``group_loss_workspace``; allocated when None) -- the stable in-tree radix sort over ``key_bits``, a
+    sort error goes to the sticky device error word (``check_device_errors``); capturable after one eager call on
+    the device.  CPU: a stable sort.  The plan depends on the batch alone, not on the model."""
+    dev = keys.device
+    n = keys.numel()
+    _chk_vec(keys, torch.int32, n, "keys", dev)
+    _check(isinstance(key_bits, int) and not isinstance(key_bits, bool) and 1 <= key_bits <= 31,
+           f"group_plan: key_bits must be an int in [1, 31], got {key_bits!r}")
+    _check(n < 2**30, "group_plan: n must be < 2^30 (the radix sort's bound)")
+    if _DEBUG and n > 0 and not (keys.is_cuda and torch.cuda.is_current_stream_capturing()):
+        _check(int(keys.max()) < (1 << key_bits) - 1, "keys: ids must be below 2^key_bits - 1")
+    if not _is_gpu(keys):
+        _check(ws is None, "group_plan: the workspace is a GPU argument")
+        sidx, first, end = (torch.empty(n, dtype=torch.int32) for _ in range(3))
+        native.cpu().group_plan(n=n, ids=_p(keys), key_bits=key_bits, sidx=_p(sidx), first=_p(first), end=_p(end))
+        return GroupPlan(n, key_bits, None, sidx, first, end)
+    h = native.hip()
+    need = int(h.group_loss_workspace_bytes(n))
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _chk_vec(ws, torch.uint8, need, "ws", dev)
+    o = h.group_plan_offsets(n)
+    sidx, first, end = (ws[o[i]: o[i] + 4 * n].view(torch.int32) for i in range(3))
+    err = ws[o[3]: o[3] + 4].view(torch.int32)
+    if n > 0:
+        _sort_selfcheck(dev)
+        h.group_plan(ids=_p(keys), n=n, key_bits=key_bits, ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(keys))
+    return GroupPlan(n, key_bits, ws, sidx, first, end, err)
+
+
+def group_softmax_loss(plan: GroupPlan, scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None,
+                       grad_scale: float = 1.0, *, dpred: torch.Tensor | None = None,
+                       ws: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Listwise softmax cross-entropy of the groups of ``plan``: ``(dpred [n] fp32, loss_sum 0-d fp32)``.
+
+    With the gain ``a_i = w_i max(y_i, 0)`` (``rank_metrics``' gain times the example weight) and, per group g over
+    its examples, ``m = max s_i, Z = sum exp(s_i - m), A = sum a_i, T = sum a_i s_i``:
+    ``L_g = A (m + log Z) - T = -sum a_i log softmax_g(s)_i``, ``dL/ds_i = A exp(s_i - m) / Z - a_i``,
+    ``dpred_i = grad_scale dL/ds_i`` and ``loss_sum = sum_g L_g``.  A group without a positive (``A == 0``), a
+    group of one and an excluded example add exactly 0 loss and 0 gradient; the gradient sums to zero within every
+    group.  Everything is fp64 (exp and log too) summed in a fixed order and rounded to fp32 once: bitwise the
+    same run to run.  GPU: hip/group_loss.hip on the current stream, no host read (capturable); ``ws``: the
+    workspace of the intermediates, the plan's own by default.  CPU: a loop over the plan."""
+    dev = scores.device
+    n = plan.n
+    _check(scores.numel() == n, f"group_softmax_loss: the plan has {n} examples, scores {scores.numel()}")
+    _chk_vec(scores, torch.float32, n, "scores", dev)
+    _chk_vec(labels, torch.float32, n, "labels", dev)
+    _chk_vec(weights, torch.float32, n, "weights", dev)
+    _check(plan.sidx.device == dev, "group_softmax_loss: the plan lives on another device")
+    if dpred is None:
+        dpred = torch.empty(n, dtype=torch.float32, device=dev)
+    _chk_vec(dpred, torch.float32, n, "dpred", dev)
+    if n == 0:
+        return dpred[:0], torch.zeros((), dtype=torch.float32, device=dev)
+    if not _is_gpu(scores):
+        _check(ws is None, "group_softmax_loss: the workspace is a GPU argument")
+        ls = native.cpu().group_softmax(n=n, sidx=_p(plan.sidx), first=_p(plan.first), end=_p(plan.end),
+                                        scores=_p(scores), labels=_p(labels), weights=_p(weights),
+                                        grad_scale=float(grad_scale), dpred=_p(dpred))
+        return dpred[:n], torch.tensor(ls, dtype=torch.float32)
+    h = native.hip()
+    if ws is None:
+        ws = plan.ws
+    _chk_vec(ws, torch.uint8, int(h.group_loss_workspace_bytes(n)), "ws", dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    h.group_softmax(plan=_p(plan.ws), plan_bytes=plan.ws.numel(), n=n, scores=_p(scores), labels=_p(labels),
+                    weights=_p(weights), grad_scale=float(grad_scale), dpred=_p(dpred), loss=_p(loss), ws=_p(ws),
+                    ws_bytes=ws.numel(), stream=_stream(scores))
+    return dpred[:n], loss
+
+
+# ---------------------------------------------------------------------------
 # calibration: exact isotonic regression of (score, label, weight)
 # ---------------------------------------------------------------------------
 class IsotonicFit(_SortedScoreRecord):
