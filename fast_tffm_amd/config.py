@@ -38,10 +38,12 @@ Extensions (new keys, all optional):
                 validation_ap = true|false (average precision of the validation scores, weighted like the loss,
                                 printed and logged after those lines; default false), ap_tolerance = <float>
                                 (stop when it is >= this; needs validation_ap and validation_files),
-                loss_type = mse|logistic|rank_softmax (rank_softmax: the listwise loss, a softmax cross-entropy
-                                per group over the examples of one batch; local mode, one rank),
-                rank_group_feature = <P> (rank_softmax only: an example's group key is the table row of its P-th
-                                feature, 0-based; default 0; examples with fewer features are left out),
+                loss_type = mse|logistic|rank_softmax|rank_pairwise (rank_softmax: the listwise loss, a softmax
+                                cross-entropy per group over the examples of one batch; rank_pairwise: the
+                                logistic loss of every (positive, negative) pair of such a group, the smooth
+                                surrogate of GAUC; both: local mode, one rank),
+                rank_group_feature = <P> (the two rank losses only: an example's group key is the table row of its
+                                P-th feature, 0-based; default 0; examples with fewer features are left out),
                 checkpoint_format = dense|sparse (sparse: a checkpoint stores only the rows that differ from
                                 their counter-based init, and restore regenerates the others; default dense)
   [Predict]     predict_group_files = <files> (one group key per line, parallel to predict_files: the
@@ -81,6 +83,7 @@ GENERAL, TRAIN, PREDICT, DISTRIBUTED = "General", "Train", "Predict", "Distribut
 
 
 _TABLE_DTYPES = ("fp32", "bf16", "fp8")  # -> torch.float32 / bfloat16 / float8_e4m3fn
+RANK_LOSSES = ("rank_softmax", "rank_pairwise")  # ops/kernels.py RANK_LOSSES: the group losses of one batch
 
 class ConfigError(ValueError):
     pass
@@ -117,8 +120,8 @@ class FMRunConfig:
     num_epochs: int = 10
     learning_rate: float = 0.01
     adagrad_init_accumulator: float = 0.1
-    loss_type: str = "mse"      # mse | logistic | rank_softmax (listwise, per group of one batch)
-    rank_group_feature: int = 0  # rank_softmax: the feature position whose table row is the group key
+    loss_type: str = "mse"      # mse | logistic | rank_softmax (listwise) | rank_pairwise: per group of one batch
+    rank_group_feature: int = 0  # rank losses: the feature position whose table row is the group key
     save_steps: int = 100
     queue_size: int = 10000
     shuffle_threads: int = 1
@@ -302,12 +305,13 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
     if c.checkpoint_format not in ("dense", "sparse"):
         raise ConfigError(f"[Train] checkpoint_format must be dense or sparse, got {c.checkpoint_format}")
 
-    if c.loss_type not in ("logistic", "mse", "rank_softmax"):
-        raise ConfigError("loss_type must be 'logistic', 'mse' or 'rank_softmax', got %r" % c.loss_type)
+    if c.loss_type not in ("logistic", "mse") + RANK_LOSSES:
+        raise ConfigError("loss_type must be 'logistic', 'mse', 'rank_softmax' or 'rank_pairwise', got %r"
+                          % c.loss_type)
     rgf = read(TRAIN, "rank_group_feature", required=False)
     if rgf is not None:
-        if c.loss_type != "rank_softmax":
-            raise ConfigError("rank_group_feature needs loss_type = rank_softmax.")
+        if c.loss_type not in RANK_LOSSES:
+            raise ConfigError("rank_group_feature needs loss_type = rank_softmax or rank_pairwise.")
         try:
             c.rank_group_feature = int(rgf)
         except ValueError:
@@ -403,9 +407,9 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
     c.prefetch_rows = opt(DISTRIBUTED, "prefetch_rows", lambda s: s.strip().lower(), c.prefetch_rows)
     c.overlap_grads = opt(DISTRIBUTED, "overlap_grads", lambda s: s.strip().lower(), c.overlap_grads)
     c.staleness = opt(DISTRIBUTED, "staleness", int, c.staleness)
-    if c.loss_type == "rank_softmax" and c.mode not in ("auto", "local"):
-        raise ConfigError("loss_type = rank_softmax needs [Distributed] mode = local (or auto on one rank), got %s"
-                          % c.mode)
+    if c.loss_type in RANK_LOSSES and c.mode not in ("auto", "local"):
+        raise ConfigError("loss_type = %s needs [Distributed] mode = local (or auto on one rank), got %s"
+                          % (c.loss_type, c.mode))
     if c.comm_dtype not in ("auto", "storage", "fp32", "bf16"):
         raise ConfigError(f"[Distributed] comm_dtype must be auto, fp32 or bf16, got {c.comm_dtype}")
     if c.staleness not in (0, 1):

@@ -712,6 +712,59 @@ double group_softmax(int n, const int* sidx, const int* first, const int* end, c
   return loss;
 }
 
+double group_pairwise(int n, const int* sidx, const int* first, const int* end, const float* scores,
+                      const float* labels, const float* weights, double grad_scale, float* dpred) {
+  double loss = 0.0;
+  std::vector<double> cw;  // the group's signed class weights: +p, -q, 0
+  for (int j = 0; j < n;) {
+    if (end[j] == 0) {
+      dpred[sidx[j]] = 0.f;
+      ++j;
+      continue;
+    }
+    const int e = end[j], m = e - j;
+    cw.assign(m, 0.0);
+    double P = 0.0, N = 0.0;
+    for (int q = 0; q < m; ++q) {
+      const int ex = sidx[j + q];
+      const double w = weights ? static_cast<double>(weights[ex]) : 1.0;
+      if (!(w > 0.0)) continue;
+      if (labels[ex] > 0.f) {
+        P += w;
+        cw[q] = w;
+      } else {
+        N += w;
+        cw[q] = -w;
+      }
+    }
+    const bool valid = P > 0.0 && N > 0.0;
+    const double c = valid ? (P + N) / (P * N) : 0.0;
+    for (int q = 0; q < m; ++q) {
+      const int ex = sidx[j + q];
+      double d = 0.0;
+      if (valid && cw[q] != 0.0) {
+        const bool pos = cw[q] > 0.0;
+        const double s = scores[ex];
+        double sig = 0.0, sp = 0.0;
+        for (int k = 0; k < m; ++k) {
+          if (pos ? !(cw[k] < 0.0) : !(cw[k] > 0.0)) continue;
+          const double sk = scores[sidx[j + k]];
+          const double df = pos ? sk - s : s - sk;  // s_neg - s_pos
+          const double t = std::exp(-std::fabs(df));
+          const double aw = std::fabs(cw[k]);
+          sig += aw * ((df >= 0.0 ? 1.0 : t) / (1.0 + t));
+          if (pos) sp += aw * (std::fmax(df, 0.0) + std::log1p(t));
+        }
+        d = -(c * cw[q]) * sig;
+        if (pos) loss += (c * cw[q]) * sp;
+      }
+      dpred[ex] = static_cast<float>(grad_scale * d);
+    }
+    j = e;
+  }
+  return loss;
+}
+
 namespace {
 template <typename T>
 void isotonic_pass(const std::vector<uint64_t>& kv, const float* labels, const float* weights, uint64_t nans,

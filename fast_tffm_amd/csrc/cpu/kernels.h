@@ -100,6 +100,14 @@ void group_plan(int n, const int* ids, int key_bits, int* sidx, int* first, int*
 double group_softmax(int n, const int* sidx, const int* first, const int* end, const float* scores,
                      const float* labels, const float* weights, double grad_scale, float* dpred);
 
+// Pairwise ranking loss (hip/group_pair.hip: same definition, fp64, a loop over the plan's groups): positive iff
+// y > 0, p = w of a positive, q = w of a non-positive, c = (P + N) / (P N); dpred[n] (example order) =
+// fp32(grad_scale (-+) c w sum of the opposite class's weights times sigma(s_neg - s_pos)); returns sum_g c sum
+// p_i q_j softplus(s_j - s_i).  A group without a positive or without a negative, an excluded example and an
+// example of weight 0 add exactly 0 and get exactly 0, whatever their scores hold.
+double group_pairwise(int n, const int* sidx, const int* first, const int* end, const float* scores,
+                      const float* labels, const float* weights, double grad_scale, float* dpred);
+
 // Exact isotonic regression (hip/isotonic.hip: same definition, same two modes) of n >= 1 scores, weights null
 // or all > 0: the blocks' first / last score lo, hi, weight W, positive weight Y (uint64 when weights is null,
 // else fp64 summed in sorted order) and value v = Y / W (fp64), [n] each; out[5] = blocks, total weight, positive

@@ -554,6 +554,16 @@ PYBIND11_MODULE(_fm_cpu, m) {
       },
       py::arg("n"), py::arg("sidx"), py::arg("first"), py::arg("end"), py::arg("scores"), py::arg("labels"),
       py::arg("weights"), py::arg("grad_scale"), py::arg("dpred"));
+  m.def(
+      "group_pairwise",
+      [](int n, u64 sidx, u64 first, u64 end, u64 scores, u64 labels, u64 weights, double grad_scale, u64 dpred) {
+        py::gil_scoped_release nogil;
+        return fm::cpu::group_pairwise(n, P<const int>(sidx), P<const int>(first), P<const int>(end),
+                                       P<const float>(scores), P<const float>(labels), P<const float>(weights),
+                                       grad_scale, P<float>(dpred));
+      },
+      py::arg("n"), py::arg("sidx"), py::arg("first"), py::arg("end"), py::arg("scores"), py::arg("labels"),
+      py::arg("weights"), py::arg("grad_scale"), py::arg("dpred"));
 
   m.def(
       "isotonic",

@@ -34,6 +34,7 @@ using u64 = std::uintptr_t;
 #include "gauc.hip"
 #include "rank_metrics.hip"
 #include "group_loss.hip"
+#include "group_pair.hip"
 #include "shard.hip"
 #include "init.hip"
 #include "ckpt.hip"
@@ -506,6 +507,30 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
                                        P<const float>(labels), P<const float>(weights), grad_scale, P<float>(dpred),
                                        P<float>(loss), P<void>(ws), ws_bytes, S(stream)),
               "group_softmax");
+      },
+      py::arg("plan"), py::arg("plan_bytes"), py::arg("n"), py::arg("scores"), py::arg("labels"), py::arg("weights"),
+      py::arg("grad_scale"), py::arg("dpred"), py::arg("loss"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
+
+  m.attr("GROUP_PAIR_ROWS") = fm::kGlTile;      // sorted positions per row tile of the pairwise loss
+  m.attr("GROUP_PAIR_CHUNK") = fm::kGpChunk;    // columns per chunk (chunks start at multiples of it)
+  m.attr("GROUP_PAIR_SLABS") = fm::kGpSlabs;    // column slabs of a row tile's span
+  m.def(
+      "group_pair_workspace_bytes",
+      [](long long n) {
+        const size_t b = fm::group_pair_workspace_bytes(n);
+        if (!b) throw std::invalid_argument("group pair loss: n must be in [0, 2^30)");
+        return b;
+      },
+      py::arg("n"));
+  m.def(
+      "group_pairwise",  // the pairwise score half: dpred[n] (example order) and loss[1] (fp32) from a plan (read
+                         // only) into a workspace of its own; asynchronous
+      [](u64 plan, size_t plan_bytes, int n, u64 scores, u64 labels, u64 weights, double grad_scale, u64 dpred,
+         u64 loss, u64 ws, size_t ws_bytes, u64 stream) {
+        check(fm::launch_group_pairwise(P<const void>(plan), plan_bytes, n, P<const float>(scores),
+                                        P<const float>(labels), P<const float>(weights), grad_scale, P<float>(dpred),
+                                        P<float>(loss), P<void>(ws), ws_bytes, S(stream)),
+              "group_pairwise");
       },
       py::arg("plan"), py::arg("plan_bytes"), py::arg("n"), py::arg("scores"), py::arg("labels"), py::arg("weights"),
       py::arg("grad_scale"), py::arg("dpred"), py::arg("loss"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));

@@ -9,7 +9,8 @@ Here the step is an explicit pipeline of native kernels, no autograd graph:
   local (world == 1):   fwd+loss (direct table gather) | dedup -> bwd+optimizer
                         (loss_type = rank_softmax: fwd scores | dedup + group plan -> listwise loss -> bwd;
                         the plan half of ops.kernels.group_softmax_loss depends on the batch alone and travels
-                        with the batch's dedup, the score half sits between forward and backward)
+                        with the batch's dedup, the score half sits between forward and backward;
+                        loss_type = rank_pairwise: the same plan, ops.kernels.group_pairwise_loss in that slot)
   shard (row-sharded):  dedup -> a2a(ids) -> owner gather -> a2a(rows) -> fwd
                         -> bwd(emit grads) -> a2a(grads) -> owner sum+optimizer
   dp    (replicated):   local fwd/bwd(emit) -> all_gather(ids, grads) -> every
@@ -61,8 +62,9 @@ def side_stream(device):
 class FMConfig:
     vocabulary_size: int
     factor_num: int
-    loss_type: str = "mse"            # "mse" | "logistic" | "rank_softmax" (listwise; local mode, one rank)
-    rank_group_feature: int = 0       # rank_softmax: an example's group key = the table row of this feature position
+    loss_type: str = "mse"            # "mse" | "logistic" | "rank_softmax" (listwise) | "rank_pairwise" (the rank
+                                      # losses: local mode, one rank)
+    rank_group_feature: int = 0       # rank losses: an example's group key = the table row of this feature position
     factor_lambda: float = 0.0
     bias_lambda: float = 0.0
     batch_size: int = 50000           # configured batch size: reg_score / batch_size (fm_model.py:345-347)
@@ -87,10 +89,12 @@ class _Workspace:
     """Per-step buffers, grown on demand and then reused (no per-step allocation)."""
 
     def __init__(self, device: torch.device, Kp: int, CH: int, r1_dtype: torch.dtype = torch.float32,
-                 group_loss: bool = False):
+                 group_loss: bool = False, pair_loss: bool = False):
         self.device, self.Kp, self.CH, self.r1_dtype = device, Kp, CH, r1_dtype
         self.cap_b = self.cap_n = 0
-        self.group = _GroupBufs() if group_loss else None  # listwise loss only: its plan of the unplanned step
+        self.group = _GroupBufs() if group_loss else None  # rank losses only: the plan of the unplanned step
+        self.pair_ws = None   # pairwise loss only (GPU): the workspace of its score half
+        self._pair_loss = pair_loss
 
     def ensure(self, B: int, nnz: int) -> None:
         dev, Kp = self.device, self.Kp
@@ -102,6 +106,8 @@ class _Workspace:
             self.cap_b = cap
             if self.group is not None:
                 self.group.ensure(cap, dev)
+            if self._pair_loss and dev.type == "cuda":
+                self.pair_ws = K.group_pair_workspace(cap, dev)
         if nnz > self.cap_n:
             cap = max(nnz, int(self.cap_n * 1.25), 1)
             self.dd = K.DedupWorkspace(cap, dev, self.CH)
@@ -113,8 +119,9 @@ class _Workspace:
             self.fwd_partial = torch.zeros(3 * 4096, dtype=torch.float32, device=dev)
 
 class _GroupBufs:
-    """Buffers of one batch's group plan (listwise loss): the examples' group keys and the workspace both halves of
-    ``K.group_softmax_loss`` use.  Allocated by models with ``loss_type = rank_softmax`` only."""
+    """Buffers of one batch's group plan (rank losses): the examples' group keys and the workspace both halves of
+    ``K.group_softmax_loss`` use (``K.group_pairwise_loss`` reads the plan there; its own intermediates live in the
+    step workspace's ``pair_ws``).  Allocated by models with a rank loss only."""
 
     def __init__(self):
         self.keys: torch.Tensor | None = None
@@ -287,12 +294,14 @@ class FactorizationMachine:
         if mode == "local" and self.world > 1:
             raise ValueError("mode=local needs world_size == 1")
         self.mode = mode
-        self.rank_loss = cfg.loss_type == K.RANK_LOSS
+        self.rank_loss = cfg.loss_type in K.RANK_LOSSES
+        self.pair_loss = cfg.loss_type == K.RANK_PAIR_LOSS
         if self.rank_loss and (mode != "local" or self.world > 1):
-            raise ValueError(f"loss_type = {K.RANK_LOSS} needs mode = local and world_size == 1 (groups are formed "
+            raise ValueError(f"loss_type = {cfg.loss_type} needs mode = local and world_size == 1 (groups are formed "
                              f"within one rank's batch), got mode = {mode}, world_size = {self.world}")
         if not self.rank_loss and cfg.rank_group_feature != 0:
-            raise ValueError(f"rank_group_feature needs loss_type = {K.RANK_LOSS}, got loss_type = {cfg.loss_type}")
+            raise ValueError(f"rank_group_feature needs loss_type = {' or '.join(K.RANK_LOSSES)}, got loss_type = "
+                             f"{cfg.loss_type}")
         if cfg.rank_group_feature < 0:
             raise ValueError(f"rank_group_feature must be >= 0, got {cfg.rank_group_feature}")
         sharded = mode == "shard"
@@ -309,7 +318,7 @@ class FactorizationMachine:
         self.K, self.Kp = self.table.K, self.table.Kp
         self.rps = rows_per_shard(cfg.vocabulary_size, self.world) if sharded else cfg.vocabulary_size
         self.ws = _Workspace(self.device, self.Kp, cfg.dedup_chunk, K.r1_dtype(cfg.dtype),
-                             group_loss=self.rank_loss)
+                             group_loss=self.rank_loss, pair_loss=self.pair_loss)
         self.global_step = 0
         self._side = None
         # lookahead dedup plans (eager local path): the current step's plan and up to two pending
@@ -579,8 +588,13 @@ class FactorizationMachine:
                               bias=self.gbias, **extra)
             if gplan_ready is not None:
                 gplan_ready()
-            dpred, loss_sum = K.group_softmax_loss(gplan, fo.pred[: sb.B], sb.labels, sb.weights,
-                                                   self.grad_scale(total_B), dpred=ws.dpred[e0:e1])
+            if self.pair_loss:
+                dpred, loss_sum = K.group_pairwise_loss(gplan, fo.pred[: sb.B], sb.labels, sb.weights,
+                                                        self.grad_scale(total_B), dpred=ws.dpred[e0:e1],
+                                                        ws=ws.pair_ws)
+            else:
+                dpred, loss_sum = K.group_softmax_loss(gplan, fo.pred[: sb.B], sb.labels, sb.weights,
+                                                       self.grad_scale(total_B), dpred=ws.dpred[e0:e1])
             return K.FwdOut(fo.pred, fo.r1, dpred, loss_sum, None, None)
         return K.fm_forward(sb.offsets, rows, sb.vals, src_v, src_w, self.Kp, labels=sb.labels, weights=sb.weights,
                             loss=cfg.loss_type, grad_scale=self.grad_scale(total_B), want_r1=True,
@@ -749,21 +763,22 @@ class FactorizationMachine:
         if self.closed and self.mode != "local":
             raise RuntimeError("forward on a closed multi-rank FactorizationMachine")
         if self.mode == "shard":
-            if loss == K.RANK_LOSS:
-                raise ValueError(f"loss = {K.RANK_LOSS} needs mode = local (groups are formed within one rank's batch)")
+            if loss in K.RANK_LOSSES:
+                raise ValueError(f"loss = {loss} needs mode = local (groups are formed within one rank's batch)")
             return self._exchange.forward(b, loss=loss, want_reg=want_reg, want_r1=want_r1)
         return self._local_forward(b, loss=loss, want_reg=want_reg, want_r1=want_r1)
 
     def _local_forward(self, b: Batch, *, loss: str, want_reg: bool, want_r1: bool) -> K.FwdOut:
         """``forward`` on this rank's own table: the local model and the replicas of dp / dp_dense."""
         rows = b.ids.to(torch.int32)
-        if loss == K.RANK_LOSS:  # the listwise loss of the batch's groups (the training step's key rule)
+        if loss in K.RANK_LOSSES:  # a rank loss of the batch's groups (the training step's key rule)
             fo = K.fm_forward(b.offsets, rows, b.vals, self.table.v, self.table.w, self.Kp, loss="none",
                               want_r1=want_r1, want_reg=want_reg, threads=self.cfg.threads, bias=self.gbias,
                               max_feats=b.max_feats)
             keys = K.group_keys(b.offsets, rows, self.cfg.rank_group_feature, self.table.rows)
             plan = K.group_plan(keys, bits_for(self.table.rows + 1))
-            fo.dpred, fo.loss_sum = K.group_softmax_loss(plan, fo.pred, b.labels, b.weights, 1.0)
+            op = K.group_pairwise_loss if loss == K.RANK_PAIR_LOSS else K.group_softmax_loss
+            fo.dpred, fo.loss_sum = op(plan, fo.pred, b.labels, b.weights, 1.0)
             return fo
         return K.fm_forward(b.offsets, rows, b.vals, self.table.v, self.table.w, self.Kp, labels=b.labels,
                             weights=b.weights, loss=loss, grad_scale=1.0, want_r1=want_r1, want_reg=want_reg,

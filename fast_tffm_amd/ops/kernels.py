@@ -1655,6 +1655,71 @@ def group_softmax_loss(plan: GroupPlan, scores: torch.Tensor, labels: torch.Tens
 
 
 # ---------------------------------------------------------------------------
+# pairwise ranking loss: logistic loss of every (positive, negative) pair of a group of one batch
+# ---------------------------------------------------------------------------
+RANK_PAIR_LOSS = "rank_pairwise"  # [Train] loss_type: the second group loss over the same plan
+RANK_LOSSES = (RANK_LOSS, RANK_PAIR_LOSS)
+
+
+def group_pair_geometry() -> tuple[int, int, int]:
+    """``(rows, chunk, slabs)`` of the GPU op (hip/group_pair.hip): sorted positions per row tile, columns per
+    chunk (chunks start at multiples of it), column slabs of a row tile's span -- where its tests put their sizes."""
+    h = native.hip()
+    return int(h.GROUP_PAIR_ROWS), int(h.GROUP_PAIR_CHUNK), int(h.GROUP_PAIR_SLABS)
+
+
+def group_pair_workspace(n: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of ``group_pairwise_loss`` for up to ``n`` examples (GPU); the plan's workspace is not it."""
+    return torch.empty(int(native.hip().group_pair_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def group_pairwise_loss(plan: GroupPlan, scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None,
+                        grad_scale: float = 1.0, *, dpred: torch.Tensor | None = None,
+                        ws: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """Pairwise logistic loss of the groups of ``plan``: ``(dpred [n] fp32, loss_sum 0-d fp32)``.
+
+    Example i is positive iff ``y_i > 0``; ``p_i = w_i`` for a positive (else 0), ``q_i = w_i`` for a non-positive
+    (else 0); per group g over its examples ``P = sum p_i, N = sum q_j, c = (P + N) / (P N)``:
+    ``L_g = c sum_{i,j} p_i q_j softplus(s_j - s_i)``, ``dL/ds_i = -c p_i sum_j q_j sigma(s_j - s_i)`` for a
+    positive, ``dL/ds_j = +c q_j sum_i p_i sigma(s_j - s_i)`` for a negative, ``dpred_i = grad_scale dL/ds_i`` and
+    ``loss_sum = sum_g L_g``.  ``L_g / ln 2 >= W_g (1 - AUC_g)`` with ``gauc``'s ``W_g = P + N``.  A group without
+    a positive or without a negative, a group of one, an excluded example and an example of weight 0 add exactly 0
+    loss and get exactly 0 gradient, whatever their scores hold; the gradient sums to zero within every group.
+    Everything is fp64 (exp, log1p and the division too), sums of non-negative terms in a fixed order, rounded to
+    fp32 once: bitwise the same run to run.  The cost is ``sum_g P_g N_g`` pairs.  GPU: hip/group_pair.hip on the
+    current stream, no host read (capturable); the plan is only read; ``ws``: ``group_pair_workspace`` (allocated
+    when None).  CPU: a loop over the plan."""
+    dev = scores.device
+    n = plan.n
+    _check(scores.numel() == n, f"group_pairwise_loss: the plan has {n} examples, scores {scores.numel()}")
+    _chk_vec(scores, torch.float32, n, "scores", dev)
+    _chk_vec(labels, torch.float32, n, "labels", dev)
+    _chk_vec(weights, torch.float32, n, "weights", dev)
+    _check(plan.sidx.device == dev, "group_pairwise_loss: the plan lives on another device")
+    if dpred is None:
+        dpred = torch.empty(n, dtype=torch.float32, device=dev)
+    _chk_vec(dpred, torch.float32, n, "dpred", dev)
+    if n == 0:
+        return dpred[:0], torch.zeros((), dtype=torch.float32, device=dev)
+    if not _is_gpu(scores):
+        _check(ws is None, "group_pairwise_loss: the workspace is a GPU argument")
+        ls = native.cpu().group_pairwise(n=n, sidx=_p(plan.sidx), first=_p(plan.first), end=_p(plan.end),
+                                         scores=_p(scores), labels=_p(labels), weights=_p(weights),
+                                         grad_scale=float(grad_scale), dpred=_p(dpred))
+        return dpred[:n], torch.tensor(ls, dtype=torch.float32)
+    h = native.hip()
+    need = int(h.group_pair_workspace_bytes(n))
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _chk_vec(ws, torch.uint8, need, "ws", dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    h.group_pairwise(plan=_p(plan.ws), plan_bytes=plan.ws.numel(), n=n, scores=_p(scores), labels=_p(labels),
+                     weights=_p(weights), grad_scale=float(grad_scale), dpred=_p(dpred), loss=_p(loss), ws=_p(ws),
+                     ws_bytes=ws.numel(), stream=_stream(scores))
+    return dpred[:n], loss
+
+
+# ---------------------------------------------------------------------------
 # calibration: exact isotonic regression of (score, label, weight)
 # ---------------------------------------------------------------------------
 class IsotonicFit(_SortedScoreRecord):
