@@ -38,12 +38,15 @@ Extensions (new keys, all optional):
                 validation_ap = true|false (average precision of the validation scores, weighted like the loss,
                                 printed and logged after those lines; default false), ap_tolerance = <float>
                                 (stop when it is >= this; needs validation_ap and validation_files),
-                loss_type = mse|logistic|rank_softmax|rank_pairwise (rank_softmax: the listwise loss, a softmax
-                                cross-entropy per group over the examples of one batch; rank_pairwise: the
-                                logistic loss of every (positive, negative) pair of such a group, the smooth
-                                surrogate of GAUC; both: local mode, one rank),
-                rank_group_feature = <P> (the two rank losses only: an example's group key is the table row of its
+                loss_type = mse|logistic|rank_softmax|rank_pairwise|rank_lambda (rank_softmax: the listwise loss,
+                                a softmax cross-entropy per group over the examples of one batch; rank_pairwise:
+                                the logistic loss of every (positive, negative) pair of such a group, the smooth
+                                surrogate of GAUC; rank_lambda: LambdaRank, the pairs of different gains weighted
+                                by the NDCG@K a swap would move, no weight_files; all: local mode, one rank),
+                rank_group_feature = <P> (the rank losses only: an example's group key is the table row of its
                                 P-th feature, 0-based; default 0; examples with fewer features are left out),
+                rank_lambda_cutoff = <K> (rank_lambda only: the K of that NDCG@K, 1..4096, or 0 for no
+                                truncation; default 10),
                 checkpoint_format = dense|sparse (sparse: a checkpoint stores only the rows that differ from
                                 their counter-based init, and restore regenerates the others; default dense)
   [Predict]     predict_group_files = <files> (one group key per line, parallel to predict_files: the
@@ -83,7 +86,9 @@ GENERAL, TRAIN, PREDICT, DISTRIBUTED = "General", "Train", "Predict", "Distribut
 
 
 _TABLE_DTYPES = ("fp32", "bf16", "fp8")  # -> torch.float32 / bfloat16 / float8_e4m3fn
-RANK_LOSSES = ("rank_softmax", "rank_pairwise")  # ops/kernels.py RANK_LOSSES: the group losses of one batch
+RANK_LOSSES = ("rank_softmax", "rank_pairwise", "rank_lambda")  # ops/kernels.py GROUP_LOSSES: the group losses of
+                                                                 # one batch
+RANK_LAMBDA_MAX_CUTOFF = 4096  # ops/kernels.py RANK_LAMBDA_MAX_CUTOFF
 
 class ConfigError(ValueError):
     pass
@@ -120,8 +125,10 @@ class FMRunConfig:
     num_epochs: int = 10
     learning_rate: float = 0.01
     adagrad_init_accumulator: float = 0.1
-    loss_type: str = "mse"      # mse | logistic | rank_softmax (listwise) | rank_pairwise: per group of one batch
+    loss_type: str = "mse"      # mse | logistic | rank_softmax (listwise) | rank_pairwise | rank_lambda: per group
+                                # of one batch
     rank_group_feature: int = 0  # rank losses: the feature position whose table row is the group key
+    rank_lambda_cutoff: int = 10  # rank_lambda: the K of the NDCG@K its pairs are weighted by (0: no truncation)
     save_steps: int = 100
     queue_size: int = 10000
     shuffle_threads: int = 1
@@ -189,7 +196,7 @@ class FMRunConfig:
         else:
             opt = OptConfig(self.optimizer, lr=self.learning_rate, initial_accumulator=self.adagrad_init_accumulator)
         return FMConfig(vocabulary_size=self.vocabulary_size, factor_num=self.factor_num, loss_type=self.loss_type,
-                        rank_group_feature=self.rank_group_feature,
+                        rank_group_feature=self.rank_group_feature, rank_lambda_cutoff=self.rank_lambda_cutoff,
                         factor_lambda=self.factor_lambda, bias_lambda=self.bias_lambda, batch_size=self.batch_size,
                         init_value_range=self.init_value_range, seed=self.seed,
                         dtype={"fp32": torch.float32, "bf16": torch.bfloat16,
@@ -306,18 +313,29 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
         raise ConfigError(f"[Train] checkpoint_format must be dense or sparse, got {c.checkpoint_format}")
 
     if c.loss_type not in ("logistic", "mse") + RANK_LOSSES:
-        raise ConfigError("loss_type must be 'logistic', 'mse', 'rank_softmax' or 'rank_pairwise', got %r"
-                          % c.loss_type)
+        raise ConfigError("loss_type must be 'logistic', 'mse', 'rank_softmax', 'rank_pairwise' or 'rank_lambda', "
+                          "got %r" % c.loss_type)
     rgf = read(TRAIN, "rank_group_feature", required=False)
     if rgf is not None:
         if c.loss_type not in RANK_LOSSES:
-            raise ConfigError("rank_group_feature needs loss_type = rank_softmax or rank_pairwise.")
+            raise ConfigError("rank_group_feature needs loss_type = rank_softmax, rank_pairwise or rank_lambda.")
         try:
             c.rank_group_feature = int(rgf)
         except ValueError:
             c.rank_group_feature = -1
         if c.rank_group_feature < 0:
             raise ConfigError("rank_group_feature must be an integer >= 0, got %s." % rgf.strip())
+    rlc = read(TRAIN, "rank_lambda_cutoff", required=False)
+    if rlc is not None:
+        if c.loss_type != "rank_lambda":
+            raise ConfigError("rank_lambda_cutoff needs loss_type = rank_lambda.")
+        try:
+            c.rank_lambda_cutoff = int(rlc)
+        except ValueError:
+            c.rank_lambda_cutoff = -1
+        if not 0 <= c.rank_lambda_cutoff <= RANK_LAMBDA_MAX_CUTOFF:
+            raise ConfigError("rank_lambda_cutoff must be 0 (no truncation) or an integer in 1..%d, got %s."
+                              % (RANK_LAMBDA_MAX_CUTOFF, rlc.strip()))
     if c.optimizer not in ("adagrad", "ftrl", "sgd"):
         raise ConfigError("optimizer must be adagrad|ftrl|sgd, got %r" % c.optimizer)
     if c.dtype not in _TABLE_DTYPES:
@@ -329,6 +347,9 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
         c.weight_files = _expand(wf, base_dir)
         if len(c.train_files) != len(c.weight_files):
             raise ConfigError("The numbers of train files and weight files do not match.")
+        if c.loss_type == "rank_lambda":
+            raise ConfigError("loss_type = rank_lambda takes no weight_files (example weights are no input of the "
+                              "NDCG it trains, as they are none of the ranking metrics).")
 
     vf = read_list(TRAIN, "validation_files", required=False)
     if vf is not None:

@@ -3,6 +3,7 @@
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <functional>
 #include <limits>
 #include <numeric>
 #include <type_traits>
@@ -759,6 +760,75 @@ double group_pairwise(int n, const int* sidx, const int* first, const int* end, 
         if (pos) loss += (c * cw[q]) * sp;
       }
       dpred[ex] = static_cast<float>(grad_scale * d);
+    }
+    j = e;
+  }
+  return loss;
+}
+
+double group_lambda(int n, const int* sidx, const int* first, const int* end, const float* scores,
+                    const float* labels, int cutoff, double grad_scale, float* dpred) {
+  (void)first;
+  double loss = 0.0;
+  const auto disc = [cutoff](int place) {
+    return (cutoff == 0 || place <= cutoff) ? 1.0 / std::log2(static_cast<double>(place) + 1.0) : 0.0;
+  };
+  std::vector<int> ord;                // the group's members by score descending, ties in example order
+  std::vector<uint32_t> key;
+  std::vector<double> gain, sorted_gain, c;
+  for (int j = 0; j < n;) {
+    if (end[j] == 0) {
+      dpred[sidx[j]] = 0.f;
+      ++j;
+      continue;
+    }
+    const int e = end[j], m = e - j;
+    gain.assign(m, 0.0);
+    for (int q = 0; q < m; ++q) {
+      const float y = labels[sidx[j + q]];
+      if (y > 0.f) gain[q] = static_cast<double>(y);
+    }
+    sorted_gain = gain;
+    std::stable_sort(sorted_gain.begin(), sorted_gain.end(), std::greater<double>());
+    double idcg = 0.0;
+    for (int q = 0; q < m; ++q) idcg += sorted_gain[q] * disc(q + 1);
+    if (m < 2 || !(idcg > 0.0)) {  // nothing to rank: exact zeros, the scores are not read
+      for (int q = 0; q < m; ++q) dpred[sidx[j + q]] = 0.f;
+      j = e;
+      continue;
+    }
+    ord.resize(m);
+    key.resize(m);
+    for (int q = 0; q < m; ++q) {
+      ord[q] = q;  // the plan keeps a group in example order: position order is example order
+      uint32_t b;
+      std::memcpy(&b, &scores[sidx[j + q]], 4);
+      key[q] = score_key(b);
+    }
+    std::stable_sort(ord.begin(), ord.end(), [&](int a, int b) { return key[a] > key[b]; });
+    c.assign(m, 0.0);
+    for (int r = 0; r < m; ++r) c[ord[r]] = disc(r + 1);
+    for (int q = 0; q < m; ++q) {
+      const int ex = sidx[j + q];
+      const double s = scores[ex];
+      double up = 0.0, dn = 0.0, sp = 0.0;
+      for (int k = 0; k < m; ++k) {
+        if (gain[k] == gain[q] || c[k] == c[q]) continue;
+        const bool larger = gain[q] > gain[k];
+        const double dl = std::fabs(gain[q] - gain[k]) * std::fabs(c[q] - c[k]);
+        const double sk = scores[sidx[j + k]];
+        const double df = larger ? sk - s : s - sk;  // s of the smaller gain - s of the larger
+        const double t = std::exp(-std::fabs(df));
+        const double sg = dl * ((df >= 0.0 ? 1.0 : t) / (1.0 + t));
+        if (larger) {
+          up += sg;
+          sp += dl * (std::fmax(df, 0.0) + std::log1p(t));
+        } else {
+          dn += sg;
+        }
+      }
+      dpred[ex] = static_cast<float>(grad_scale * ((dn - up) / idcg));
+      loss += sp / idcg;
     }
     j = e;
   }

@@ -108,6 +108,16 @@ double group_softmax(int n, const int* sidx, const int* first, const int* end, c
 double group_pairwise(int n, const int* sidx, const int* first, const int* end, const float* scores,
                       const float* labels, const float* weights, double grad_scale, float* dpred);
 
+// LambdaRank loss at cutoff K (hip/group_lambda.hip: same definition, fp64, a loop over the plan's groups with a
+// stable sort per group): G = max(y, 0), place r by score descending (score_key.h's order, ties in example order),
+// c(r) = 1 / log2(r + 1) for r <= K (every r when K = 0) else 0, IDCG over the gains descending; for every pair
+// G_i > G_j: delta = (G_i - G_j) |c(r_i) - c(r_j)| / IDCG; dpred[n] (example order) = fp32(grad_scale (sum over the
+// larger gains - sum over the smaller gains of delta sigma(s_smaller - s_larger))); returns sum_g sum delta
+// softplus(s_j - s_i).  A group with IDCG == 0, a group of one and an excluded example add exactly 0 and get
+// exactly 0, whatever their scores hold.
+double group_lambda(int n, const int* sidx, const int* first, const int* end, const float* scores,
+                    const float* labels, int cutoff, double grad_scale, float* dpred);
+
 // Exact isotonic regression (hip/isotonic.hip: same definition, same two modes) of n >= 1 scores, weights null
 // or all > 0: the blocks' first / last score lo, hi, weight W, positive weight Y (uint64 when weights is null,
 // else fp64 summed in sorted order) and value v = Y / W (fp64), [n] each; out[5] = blocks, total weight, positive

@@ -566,6 +566,17 @@ PYBIND11_MODULE(_fm_cpu, m) {
       py::arg("weights"), py::arg("grad_scale"), py::arg("dpred"));
 
   m.def(
+      "group_lambda",
+      [](int n, u64 sidx, u64 first, u64 end, u64 scores, u64 labels, int cutoff, double grad_scale, u64 dpred) {
+        py::gil_scoped_release nogil;
+        return fm::cpu::group_lambda(n, P<const int>(sidx), P<const int>(first), P<const int>(end),
+                                     P<const float>(scores), P<const float>(labels), cutoff, grad_scale,
+                                     P<float>(dpred));
+      },
+      py::arg("n"), py::arg("sidx"), py::arg("first"), py::arg("end"), py::arg("scores"), py::arg("labels"),
+      py::arg("cutoff"), py::arg("grad_scale"), py::arg("dpred"));
+
+  m.def(
       "isotonic",
       [](int n, u64 scores, u64 labels, u64 weights, u64 lo, u64 hi, u64 W, u64 Y, u64 v, u64 fitted, u64 out,
          int tile) {

@@ -35,6 +35,7 @@ using u64 = std::uintptr_t;
 #include "rank_metrics.hip"
 #include "group_loss.hip"
 #include "group_pair.hip"
+#include "group_lambda.hip"
 #include "shard.hip"
 #include "init.hip"
 #include "ckpt.hip"
@@ -533,6 +534,32 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
               "group_pairwise");
       },
       py::arg("plan"), py::arg("plan_bytes"), py::arg("n"), py::arg("scores"), py::arg("labels"), py::arg("weights"),
+      py::arg("grad_scale"), py::arg("dpred"), py::arg("loss"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
+
+  m.attr("GROUP_LAMBDA_ROWS") = fm::kGlTile;          // sorted positions per row tile of the LambdaRank loss
+  m.attr("GROUP_LAMBDA_CHUNK") = fm::kGmChunk;        // columns per chunk (chunks start at multiples of it)
+  m.attr("GROUP_LAMBDA_SLABS") = fm::kGmSlabs;        // column slabs of a row tile's span
+  m.attr("GROUP_LAMBDA_MAX_CUTOFF") = fm::kGmMaxCutoff;
+  m.def(
+      "group_lambda_workspace_bytes",
+      [](long long n) {
+        const size_t b = fm::group_lambda_workspace_bytes(n);
+        if (!b) throw std::invalid_argument("group lambda loss: n must be in [0, 2^30)");
+        return b;
+      },
+      py::arg("n"));
+  m.def(
+      "group_lambda",  // the LambdaRank score half: dpred[n] (example order) and loss[1] (fp32) from a plan (read
+                       // only) into a workspace of its own; asynchronous
+      [](u64 plan, size_t plan_bytes, int n, u64 scores, u64 labels, int cutoff, double grad_scale, u64 dpred,
+         u64 loss, u64 ws, size_t ws_bytes, u64 stream) {
+        const int rc = fm::launch_group_lambda(P<const void>(plan), plan_bytes, n, P<const float>(scores),
+                                               P<const float>(labels), cutoff, grad_scale, P<float>(dpred),
+                                               P<float>(loss), P<void>(ws), ws_bytes, S(stream));
+        if (rc == -9) throw std::invalid_argument("group_lambda: the cutoff must be in [0, 4096]");
+        check(rc, "group_lambda");
+      },
+      py::arg("plan"), py::arg("plan_bytes"), py::arg("n"), py::arg("scores"), py::arg("labels"), py::arg("cutoff"),
       py::arg("grad_scale"), py::arg("dpred"), py::arg("loss"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
 
   m.def(

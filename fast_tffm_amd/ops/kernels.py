@@ -1720,6 +1720,76 @@ def group_pairwise_loss(plan: GroupPlan, scores: torch.Tensor, labels: torch.Ten
 
 
 # ---------------------------------------------------------------------------
+# LambdaRank loss: the pairs of different gains of a group of one batch, weighted by the NDCG@K a swap would move
+# ---------------------------------------------------------------------------
+RANK_LAMBDA_LOSS = "rank_lambda"  # [Train] loss_type: the third group loss over the same plan
+GROUP_LOSSES = RANK_LOSSES + (RANK_LAMBDA_LOSS,)  # every loss_type that trains on the groups of one batch
+RANK_LAMBDA_MAX_CUTOFF = 4096  # hip/group_lambda.hip kGmMaxCutoff
+
+
+def group_lambda_geometry() -> tuple[int, int, int]:
+    """``(rows, chunk, slabs)`` of the GPU op (hip/group_lambda.hip): sorted positions per row tile, columns per
+    chunk (chunks start at multiples of it), column slabs of a row tile's span -- where its tests put their sizes."""
+    h = native.hip()
+    return int(h.GROUP_LAMBDA_ROWS), int(h.GROUP_LAMBDA_CHUNK), int(h.GROUP_LAMBDA_SLABS)
+
+
+def group_lambda_workspace(n: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of ``group_lambda_loss`` for up to ``n`` examples (GPU); the plan's workspace is not it."""
+    return torch.empty(int(native.hip().group_lambda_workspace_bytes(int(n))), dtype=torch.uint8, device=device)
+
+
+def group_lambda_loss(plan: GroupPlan, scores: torch.Tensor, labels: torch.Tensor, cutoff: int,
+                      grad_scale: float = 1.0, *, dpred: torch.Tensor | None = None,
+                      ws: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """LambdaRank loss at NDCG cutoff ``cutoff`` (0: no truncation, else 1..4096) of the groups of ``plan``:
+    ``(dpred [n] fp32, loss_sum 0-d fp32)``.
+
+    ``G_i = max(y_i, 0)`` (``rank_metrics``' gain; example weights are no input); per group g, ``r_i`` the place of i
+    by score descending (equal scores in example order, ``-0.0 == +0.0``), ``c(r) = 1 / log2(r + 1)`` for
+    ``r <= cutoff`` (every r when 0) else 0, ``IDCG_g`` over the gains descending; for every pair ``G_i > G_j``:
+    ``delta_ij = (G_i - G_j) |c(r_i) - c(r_j)| / IDCG_g`` (a constant: no gradient through the places),
+    ``L_g = sum delta_ij softplus(s_j - s_i)``, ``dL/ds_i -= delta_ij sigma(s_j - s_i)``, ``dL/ds_j +=`` the same;
+    ``dpred_i = grad_scale dL/ds_i`` and ``loss_sum = sum_g L_g``.  A group with ``IDCG_g == 0``, a group of one and
+    an excluded example add exactly 0 loss and get exactly 0 gradient, whatever their scores hold; the gradient
+    sums to zero within every group.  Everything is fp64 (exp, log1p, log2 and the divisions too), sums of
+    non-negative terms in a fixed order, rounded to fp32 once: bitwise the same run to run.  The cost is four
+    stable sorts of n and about ``sum_g 2 n_g min(cutoff, n_g)`` pairs (``n_g^2`` when cutoff is 0).  GPU:
+    hip/group_lambda.hip on the current stream, no host read (capturable); the plan is only read; ``ws``:
+    ``group_lambda_workspace`` (allocated when None).  CPU: a loop over the plan."""
+    dev = scores.device
+    n = plan.n
+    cutoff = int(cutoff)
+    _check(0 <= cutoff <= RANK_LAMBDA_MAX_CUTOFF,
+           f"group_lambda_loss: the cutoff must be in [0, {RANK_LAMBDA_MAX_CUTOFF}], got {cutoff}")
+    _check(scores.numel() == n, f"group_lambda_loss: the plan has {n} examples, scores {scores.numel()}")
+    _chk_vec(scores, torch.float32, n, "scores", dev)
+    _chk_vec(labels, torch.float32, n, "labels", dev)
+    _check(plan.sidx.device == dev, "group_lambda_loss: the plan lives on another device")
+    if dpred is None:
+        dpred = torch.empty(n, dtype=torch.float32, device=dev)
+    _chk_vec(dpred, torch.float32, n, "dpred", dev)
+    if n == 0:
+        return dpred[:0], torch.zeros((), dtype=torch.float32, device=dev)
+    if not _is_gpu(scores):
+        _check(ws is None, "group_lambda_loss: the workspace is a GPU argument")
+        ls = native.cpu().group_lambda(n=n, sidx=_p(plan.sidx), first=_p(plan.first), end=_p(plan.end),
+                                       scores=_p(scores), labels=_p(labels), cutoff=cutoff,
+                                       grad_scale=float(grad_scale), dpred=_p(dpred))
+        return dpred[:n], torch.tensor(ls, dtype=torch.float32)
+    h = native.hip()
+    need = int(h.group_lambda_workspace_bytes(n))
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    _chk_vec(ws, torch.uint8, need, "ws", dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    h.group_lambda(plan=_p(plan.ws), plan_bytes=plan.ws.numel(), n=n, scores=_p(scores), labels=_p(labels),
+                   cutoff=cutoff, grad_scale=float(grad_scale), dpred=_p(dpred), loss=_p(loss), ws=_p(ws),
+                   ws_bytes=ws.numel(), stream=_stream(scores))
+    return dpred[:n], loss
+
+
+# ---------------------------------------------------------------------------
 # calibration: exact isotonic regression of (score, label, weight)
 # ---------------------------------------------------------------------------
 class IsotonicFit(_SortedScoreRecord):
