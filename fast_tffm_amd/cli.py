@@ -7,9 +7,10 @@ Same arguments as the reference's run_tffm.py (run_tffm.py:124-162):
   --dist JOB_NAME TASK_INDEX PS_HOSTS WORKER_HOSTS, --protocol, --wait-for-workers N,
   -t/--trace FILE, -m/--monitor, --export_path DIR.
 Extensions: --device {auto,cpu,cuda}, --mode {auto,local,shard,dp,dp_dense},
---max-steps N, --log-dir DIR (overrides [General] log_dir), the task ``explain CONFIG [--top N]``
+--max-steps N, --log-dir DIR (overrides [General] log_dir), the task ``explain CONFIG [--top N] [--pairs N]``
 (exact per-feature attributions of the predict files' scores: ``<file>_contrib`` and
-``<file>_importance``, trainer.Trainer.explain; the reference has no equivalent), the task
+``<file>_importance``, with ``--pairs`` every line's strongest feature pairs: ``<file>_pairs`` and
+``<file>_pair_importance``, trainer.Trainer.explain; the reference has no equivalent), the task
 ``recommend CONFIG --candidates FILE [--top N]`` (for every line of the predict files the N best lines of
 FILE by the score of both taken together: ``<file>_recommend``, trainer.Trainer.recommend), the task
 ``evaluate CONFIG`` (loss and ROC AUC of the checkpoint on the labelled predict files and, with ``[Predict]
@@ -66,6 +67,9 @@ def build_parser() -> argparse.ArgumentParser:
     p.add_argument("--top", type=int, default=None, metavar="N",
                    help="explain: keep only the N largest |contribution| tokens of every line; "
                         "recommend: candidates per line (1..128, default 10)")
+    p.add_argument("--pairs", type=int, default=None, metavar="N",
+                   help="explain: also write <file>_pairs, the N (1..64) strongest feature pairs of every line, and "
+                        "<file>_pair_importance over those pairs")
     p.add_argument("--candidates", default=None, metavar="FILE",
                    help="recommend: the candidates, one per line in the predict files' format")
     p.add_argument("--calibrated", action="store_true",
@@ -163,7 +167,7 @@ def main(argv: list[str] | None = None) -> int:
         elif args.task == "calibrate":
             tr.calibrate()
         elif args.task == "explain":
-            tr.explain(top=args.top)
+            tr.explain(top=args.top, pairs=args.pairs)
         elif args.task == "recommend":
             tr.recommend(args.candidates, top=10 if args.top is None else args.top)
         else:

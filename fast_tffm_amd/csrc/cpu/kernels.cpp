@@ -13,6 +13,7 @@
 
 #include "../hash64.h"
 #include "../iso_hull.h"
+#include "../pairs_key.h"
 #include "../rank_table.h"
 #include "../score_key.h"
 #include "../threshold_rule.h"
@@ -974,6 +975,64 @@ void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q
         idx[q * k + t] = topk::key_index(key);
         std::memcpy(&score[q * k + t], &sb, 4);
       }
+    }
+  }
+}
+
+void pairs(int B, const int* offsets, const int* rows, const float* vals, const void* v, long long v_stride, int Kp,
+           int dtype, int top, int* first, int* second, float* value, int* count, int threads) {
+  set_threads(threads);
+  std::vector<int> cols;  // pi(Kp)
+  topk::for_each_col(Kp, [&](int c) { cols.push_back(c); });
+  const size_t nc = cols.size();
+#pragma omp parallel
+  {
+    std::vector<uint64_t> heap;  // min-heap of the best `top` keys so far
+    std::vector<float> row(Kp), pv;  // pv: the example's rows, widened, columns in pi's order
+    heap.reserve(top + 1);
+    const auto gt = [](uint64_t a, uint64_t b) { return a > b; };
+#pragma omp for schedule(dynamic, 16)
+    for (int i = 0; i < B; ++i) {
+      const int s = offsets[i], n = offsets[i + 1] - s;
+      heap.clear();
+      if (n >= 2 && n <= pairs::kMaxN) {
+        pv.resize((size_t)n * nc);
+        for (int j = 0; j < n; ++j) {
+          load_row(v, (long long)rows[s + j] * v_stride, Kp, dtype, row.data());
+          for (size_t c = 0; c < nc; ++c) pv[j * nc + c] = row[cols[c]];
+        }
+        for (int j = 0; j < n; ++j) {
+          const float* a = &pv[j * nc];
+          const float xj = vals ? vals[s + j] : 1.f;
+          for (int l = j + 1; l < n; ++l) {
+            const float* b = &pv[l * nc];
+            float dot = 0.f;
+            for (size_t c = 0; c < nc; ++c) dot = std::fmaf(a[c], b[c], dot);
+            volatile float xx = xj * (vals ? vals[s + l] : 1.f);  // (two roundings as written)
+            const float p = xx * dot;
+            uint32_t bits;
+            std::memcpy(&bits, &p, 4);
+            const uint64_t key = pairs::make_key(bits, j, l);
+            if ((int)heap.size() < top) {
+              heap.push_back(key);
+              std::push_heap(heap.begin(), heap.end(), gt);
+            } else if (key > heap.front()) {
+              std::pop_heap(heap.begin(), heap.end(), gt);
+              heap.back() = key;
+              std::push_heap(heap.begin(), heap.end(), gt);
+            }
+          }
+        }
+        std::sort(heap.begin(), heap.end(), gt);
+      }
+      for (int t = 0; t < top; ++t) {
+        const uint64_t key = t < (int)heap.size() ? heap[t] : 0ull;
+        const uint32_t pb = pairs::key_value_bits(key);
+        first[(long long)i * top + t] = pairs::key_first(key);
+        second[(long long)i * top + t] = pairs::key_second(key);
+        std::memcpy(&value[(long long)i * top + t], &pb, 4);
+      }
+      count[i] = n > pairs::kMaxN ? -1 : (int)heap.size();
     }
   }
 }

@@ -36,6 +36,12 @@ void explain(int B, const int* offsets, const int* rows, const float* vals, cons
 void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q_stride, const float* C,
           long long c_stride, const float* qb, const float* cb, int* idx, float* score, int threads);
 
+// The `top` strongest pairs of every example (hip/fm_pairs.hip: same definition, bit for bit): p_jl = (x_j x_l) *
+// fmaf chain over pi(Kp) for j < l, greatest |p| first, equal |p| by ascending (j, l); first / second = -1 and
+// value = 0 past the example's pairs, count = -1 for an example longer than pairs::kMaxN (../pairs_key.h).
+void pairs(int B, const int* offsets, const int* rows, const float* vals, const void* v, long long v_stride, int Kp,
+           int dtype, int top, int* first, int* second, float* value, int* count, int threads);
+
 // Stable sort of (key, occurrence) + run-length encoding. Returns U.
 int dedup(int n, const uint32_t* keys, uint32_t* skeys, int* perm, uint32_t* uniq, int* seg_start, int* inv,
           const int* ex_of_occ, int* sorted_ex, const float* vals, float* sorted_x);

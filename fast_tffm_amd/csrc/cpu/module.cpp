@@ -349,6 +349,18 @@ PYBIND11_MODULE(_fm_cpu, m) {
       py::arg("pred"), py::arg("threads"));
 
   m.def(
+      "pairs",
+      [](int B, u64 offsets, u64 rows, u64 vals, u64 v, long long v_stride, int Kp, int dtype, int top, u64 first,
+         u64 second, u64 value, u64 count, int threads) {
+        py::gil_scoped_release nogil;
+        fm::cpu::pairs(B, P<const int>(offsets), P<const int>(rows), P<const float>(vals), P<const void>(v), v_stride,
+                       Kp, dtype, top, P<int>(first), P<int>(second), P<float>(value), P<int>(count), threads);
+      },
+      py::arg("B"), py::arg("offsets"), py::arg("rows"), py::arg("vals"), py::arg("v"), py::arg("v_stride"),
+      py::arg("Kp"), py::arg("dtype"), py::arg("top"), py::arg("first"), py::arg("second"), py::arg("value"),
+      py::arg("count"), py::arg("threads"));
+
+  m.def(
       "topk_plan",
       [](long long nq, long long nc, int k) {
         const fm::topk::Plan p = fm::topk::plan(nq, nc, k);

@@ -25,6 +25,7 @@ using u64 = std::uintptr_t;
 #include "fm_fwd.hip"
 #include "fm_explain.hip"
 #include "fm_topk.hip"
+#include "fm_pairs.hip"
 #include "dedup.hip"
 #include "metric_common.hip"
 #include "auc.hip"
@@ -155,6 +156,20 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       },
       py::arg("U"), py::arg("contrib"), py::arg("perm"), py::arg("seg_start"), py::arg("count"), py::arg("sum_abs"),
       py::arg("sum"), py::arg("stream"));
+
+  m.def(
+      "pairs",  // the `top` pairs of greatest |p_jl| of every example (fm_pairs.hip): first / second / value [B, top]
+      [](int B, u64 offsets, u64 rows, u64 vals, u64 v, long long v_stride, int Kp, int dtype, int top, u64 first,
+         u64 second, u64 value, u64 count, u64 stream) {
+        fm::PairsArgs a{};
+        a.B = B; a.offsets = P<const int>(offsets); a.rows = P<const int>(rows); a.vals = P<const float>(vals);
+        a.v = P<const void>(v); a.v_stride = v_stride; a.Kp = Kp; a.top = top; a.first = P<int>(first);
+        a.second = P<int>(second); a.value = P<float>(value); a.count = P<int>(count);
+        check(fm::launch_pairs(a, dtype, S(stream)), "fm_pairs");
+      },
+      py::arg("B"), py::arg("offsets"), py::arg("rows"), py::arg("vals"), py::arg("v"), py::arg("v_stride"),
+      py::arg("Kp"), py::arg("dtype"), py::arg("top"), py::arg("first"), py::arg("second"), py::arg("value"),
+      py::arg("count"), py::arg("stream"));
 
   m.def(
       "topk_plan",  // (slab, parts) of a top-k call: candidates per slab, partial lists per query (topk_order.h)

@@ -824,6 +824,20 @@ class FactorizationMachine:
                             bias=self.gbias, threads=self.cfg.threads)
 
     @torch.no_grad()
+    def interactions(self, b: Batch, top: int) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+        """The ``top`` strongest pair terms ``x_j x_l <v_j, v_l>`` of every example of ``b``: ``(first [B, top],
+        second [B, top], value [B, top], count [B])``, occurrence positions within the example, greatest
+        ``|value|`` first (``K.fm_pairs``; -1 / 0 past an example's pairs, ``count = -1`` for an example of more
+        than 4096 occurrences).  Row-sharded models gather the batch's rows like ``forward`` (a collective:
+        every rank calls)."""
+        if self.closed and self.mode != "local":
+            raise RuntimeError("interactions on a closed multi-rank FactorizationMachine")
+        if self.mode == "shard":
+            return self._exchange.interactions(b, top)
+        return K.fm_pairs(b.offsets, b.ids.to(torch.int32), b.vals, self.table.v, self.Kp, top,
+                          threads=self.cfg.threads)
+
+    @torch.no_grad()
     def profile(self, b: Batch) -> tuple[torch.Tensor, torch.Tensor]:
         """``(pred [B], S [B, Kp])`` of the examples of ``b``: the score and ``S = sum_j x_j v_j``, the two
         ingredients of ranking by parts.  For feature sets A and B, ``score(A + B) = score(A) + score(B) -

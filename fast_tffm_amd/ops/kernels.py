@@ -357,6 +357,63 @@ def fm_explain(offsets: torch.Tensor, rows: torch.Tensor, vals: torch.Tensor | N
     return contrib[:nnz], pred[:B]
 
 
+PAIRS_MAX_TOP = 64
+PAIRS_MAX_N = 4096
+
+
+def fm_pairs(offsets: torch.Tensor, rows: torch.Tensor, vals: torch.Tensor | None, v: torch.Tensor, Kp: int,
+             top: int, *, first: torch.Tensor | None = None, second: torch.Tensor | None = None,
+             value: torch.Tensor | None = None, count: torch.Tensor | None = None,
+             threads: int = 0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor, torch.Tensor]:
+    """The ``top`` strongest pair terms of every example of a CSR batch (hip/fm_pairs.hip; the reference has none).
+
+    For occurrences j < l of an example, ``p_jl = (x_j * x_l) * dot_jl`` with ``dot_jl`` the fmaf chain over the
+    columns of the two rows in the fixed order of csrc/topk_order.h (bf16 rows widened first), so that the score
+    is ``bias + sum_j x_j w_j + sum_{j<l} p_jl`` up to rounding.  Returns ``(first [B, top] int32, second [B, top]
+    int32, value [B, top] fp32, count [B] int32)``: occurrence positions within the example and the signed
+    ``p``, greatest ``|p|`` first, equal ``|p|`` by ascending ``(j, l)`` (-0.0 equals +0.0).  The comparison is on
+    the bit image of ``|p|``, so a NaN pair sorts first and a broken row shows.  An example with fewer than
+    ``top`` pairs returns them all (``count``) and pads with ``first = second = -1``, ``value = 0``; one with
+    more than 4096 occurrences gets ``count = -1`` and no pairs.  Bitwise the same on the GPU and the CPU;
+    no host read on the GPU, and the outputs may be the caller's (capturable).  ``rows`` are plain row indices
+    into ``v`` (table rows or gathered wire rows).  fp8 tables are not supported."""
+    dev = rows.device
+    B = offsets.numel() - 1
+    _check(isinstance(top, int) and 1 <= top <= PAIRS_MAX_TOP,
+           f"fm_pairs: top must be in 1..{PAIRS_MAX_TOP}, got {top}")
+    _check(v.dtype != FP8, "fm_pairs: fp8 tables are not supported (the pair terms are defined on fp32 / bf16 rows)")
+    _chk_vec(offsets, torch.int32, B + 1, "offsets", dev)
+    nnz = rows.numel()
+    _chk_vec(rows, torch.int32, nnz, "rows", dev)
+    _chk_vec(vals, torch.float32, nnz, "vals", dev)
+    v_stride = _chk_rows(v, Kp, "v")
+    _check(v.device == dev, "v: expected the rows' device")
+    _check(4 <= Kp <= TOPK_MAX_KP, f"fm_pairs: Kp={Kp} must be in 4..{TOPK_MAX_KP}")
+    _check(v_stride * v.element_size() < 2**32, "v: row stride must be below 4 GiB")
+    _check(nnz == 0 or v.shape[0] > 0, "rows index an empty table")
+    _range_check(rows, v.shape[0], "rows")
+    if first is None:
+        first = torch.empty((B, top), dtype=torch.int32, device=dev)
+    if second is None:
+        second = torch.empty((B, top), dtype=torch.int32, device=dev)
+    if value is None:
+        value = torch.empty((B, top), dtype=torch.float32, device=dev)
+    if count is None:
+        count = torch.empty(B, dtype=torch.int32, device=dev)
+    for t, name in ((first, "first"), (second, "second"), (value, "value")):
+        _chk_vec(t, torch.float32 if t is value else torch.int32, B * top, name, dev)
+        _check(tuple(t.shape) == (B, top), f"{name}: expected shape ({B}, {top})")
+    _chk_vec(count, torch.int32, B, "count", dev)
+    kw = dict(B=B, offsets=_p(offsets), rows=_p(rows), vals=_p(vals), v=_p(v), v_stride=v_stride, Kp=Kp,
+              dtype=dtype_code(v.dtype), top=top, first=_p(first), second=_p(second), value=_p(value),
+              count=_p(count))
+    if _is_gpu(rows):
+        native.hip().pairs(stream=_stream(rows), **kw)
+    else:
+        native.cpu().pairs(threads=threads, **kw)
+    return first, second, value, count[:B]
+
+
 # ---------------------------------------------------------------------------
 # dedup
 # ---------------------------------------------------------------------------

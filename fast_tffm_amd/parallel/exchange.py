@@ -1212,6 +1212,15 @@ class ShardExchange(_Base):
         self._slot_done(self.slots[pl.slot])
         return out
 
+    @torch.no_grad()
+    def interactions(self, b: Batch, top: int):
+        """``explain``'s gather, then the strongest pairs over the wire rows (``K.fm_pairs``): positions within
+        the example come back, so nothing needs mapping."""
+        pl, part, src_v, _ = self._eval_rows(b)
+        out = K.fm_pairs(b.offsets, part.dd.inv[: b.nnz], b.vals, src_v, self.Kp, top, threads=self.m.cfg.threads)
+        self._slot_done(self.slots[pl.slot])
+        return out
+
 
 class DPExchange(_Base):
     """Replicated table; sparse all-gather of (ids, gradient rows).  Evaluation (``forward``, ``explain``)

@@ -203,6 +203,16 @@ class ServingModel:
         contrib, pred = Kn.fm_explain(offsets, ids, vals, self.v, self.w, self.Kp, bias=bias)
         return pred.cpu().numpy(), offsets.cpu().numpy(), ids.cpu().numpy(), contrib.cpu().numpy()
 
+    def interactions(self, data_lines, top: int = 10) -> tuple[np.ndarray, ...]:
+        """``(offsets [B + 1], ids [nnz], first [B, top], second [B, top], value [B, top], count [B])``: the
+        lines parsed as ``predict`` parses them and every line's ``top`` strongest pair terms, as occurrence
+        positions within the line, greatest ``|value|`` first (``ops.kernels.fm_pairs``)."""
+        from .ops import kernels as Kn
+
+        offsets, ids, vals, _ = self._parse(data_lines)
+        out = Kn.fm_pairs(offsets, ids, vals, self.v, self.Kp, int(top))
+        return (offsets.cpu().numpy(), ids.cpu().numpy(), *(t.cpu().numpy() for t in out))
+
     def _profile(self, data_lines) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor | None]:
         """(score [B], S [B, Kp], bias or None) of the lines, on the model's device."""
         from .ops import kernels as Kn

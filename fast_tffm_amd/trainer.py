@@ -616,18 +616,24 @@ class Trainer:
 
 
     # ------------------------------------------------------------------
-    def explain(self, top: int | None = None) -> list[str]:
+    def explain(self, top: int | None = None, pairs: int | None = None) -> list[str]:
         """``run.py explain``: for every predict file, ``<file>_contrib`` (one line per example: the score, then
         ``id:contribution`` tokens in input order -- with ``top``, the ``top`` largest |contribution| of the
         line, by descending |c| then position) and ``<file>_importance`` (one line per distinct id:
         ``id count mean_abs mean``, by descending sum |c| then ascending id).  Ids are table rows (after
-        hashing / modulo).  Multi-rank runs split the examples as ``predict`` does."""
+        hashing / modulo).  Multi-rank runs split the examples as ``predict`` does.  With ``pairs`` also
+        ``<file>_pairs`` (one line per example: the score, then up to ``pairs`` tokens ``idA:idB:value``, the
+        line's strongest pair terms ``x_j x_l <v_j, v_l>``, greatest |value| first, the ids in occurrence order)
+        and ``<file>_pair_importance`` over those kept pairs (one line per unordered id pair: ``idA idB count
+        mean_abs mean``, by descending sum |value|, then idA, then idB)."""
         from .models.table import bits_for
         from .ops import kernels as K
 
         c = self.cfg
         if top is not None and top < 0:
             raise ValueError("explain: --top must be >= 0")
+        if pairs is not None and not 1 <= pairs <= K.PAIRS_MAX_TOP:
+            raise ValueError(f"explain: --pairs must be in 1..{K.PAIRS_MAX_TOP}, got {pairs}")
         if not self.restore():
             raise FileNotFoundError(f"no checkpoint found in {c.log_dir}")
         self.print("========", "explain", "========")
@@ -645,19 +651,27 @@ class Trainer:
             else:
                 imp = [np.empty(0, np.int32), np.empty(0, np.int32), np.empty(0), np.empty(0)]
             part = (pred.cpu().numpy(), contrib.cpu().numpy(), imp)
+            if pairs is not None:
+                part += tuple(t.cpu().numpy() for t in self.model.interactions(mine, pairs))
             parts = [part]
             if self.world > 1:
                 parts = [None] * self.world
                 dist.all_gather_object(parts, part, group=self.ctx.cpu_group)
+            if pairs is not None:  # (every rank holds every part: all of them stop)
+                for r, p in enumerate(parts):
+                    bad = np.flatnonzero(p[6] < 0)
+                    if bad.size:
+                        raise ValueError(f"{path}: line {r + int(bad[0]) * self.world + 1} has more than "
+                                         f"{K.PAIRS_MAX_N} features; explain --pairs cannot rank its pairs")
             if self.rank != 0:
                 continue
             offs = b.offsets.numpy().astype(np.int64)
             ids = b.ids.numpy()
             scores = np.empty(b.B, dtype=np.float32)
             full = np.empty(b.nnz, dtype=np.float32)
-            for r, (p_r, c_r, _) in enumerate(parts):
-                scores[r::self.world] = p_r
-                full[_occ_index(offs, np.arange(r, b.B, self.world))] = c_r
+            for r, p in enumerate(parts):
+                scores[r::self.world] = p[0]
+                full[_occ_index(offs, np.arange(r, b.B, self.world))] = p[1]
             out = path + "_contrib"
             with open(out, "w") as f:
                 for i in range(b.B):
@@ -683,6 +697,8 @@ class Trainer:
                     f.write(f"{uniq[k]} {count[k]} {str(np.float32(sum_abs[k] / count[k]))} "
                             f"{str(np.float32(total[k] / count[k]))}\n")
             written.append(out)
+            if pairs is not None:
+                written += _write_pairs(path, offs, ids, scores, [p[3:] for p in parts])
         self.print("Done. Contributions and importance saved to same directory as predict files")
         return written
 
@@ -803,6 +819,47 @@ def _write_group_ranks(out: str, gi, cutoffs: tuple, recs: list) -> str:
 
 
 RECOMMEND_PROFILE_BATCH = 65536  # candidate lines per forward pass of ``Trainer.recommend``
+
+
+def _write_pairs(path: str, offs: np.ndarray, ids: np.ndarray, scores: np.ndarray, parts) -> list[str]:
+    """``<path>_pairs`` and ``<path>_pair_importance`` of ``Trainer.explain`` from the ranks' ``(first, second,
+    value, count)`` (rank r holds examples r, r + world, ...).  The importance covers the kept pairs only: fp64
+    sums over the lines in file order, an unordered id pair under its smaller id first."""
+    B, world = scores.size, len(parts)
+    top = parts[0][0].shape[1]
+    first = np.empty((B, top), dtype=np.int64)
+    second = np.empty((B, top), dtype=np.int64)
+    value = np.empty((B, top), dtype=np.float32)
+    count = np.empty(B, dtype=np.int64)
+    for r, (f_r, s_r, v_r, c_r) in enumerate(parts):
+        first[r::world], second[r::world], value[r::world], count[r::world] = f_r, s_r, v_r, c_r
+    keep = np.arange(top)[None, :] < count[:, None]
+    ida = ids[(offs[:-1, None] + first)[keep]]    # (row-major: the lines in file order, best pair first)
+    idb = ids[(offs[:-1, None] + second)[keep]]
+    val = value[keep]
+    ends = np.cumsum(count)
+    out_pairs = path + "_pairs"
+    with open(out_pairs, "w") as f:
+        for i in range(B):
+            t0, t1 = ends[i] - count[i], ends[i]
+            toks = [f"{a}:{b}:{str(x)}" for a, b, x in zip(ida[t0:t1], idb[t0:t1], val[t0:t1])]
+            f.write(" ".join([str(np.float32(scores[i]))] + toks) + "\n")
+    lo, hi = np.minimum(ida, idb).astype(np.int64), np.maximum(ida, idb).astype(np.int64)
+    uniq, inv = np.unique(np.stack([lo, hi], axis=1), axis=0, return_inverse=True) if val.size else \
+        (np.empty((0, 2), np.int64), np.empty(0, np.int64))
+    inv = inv.reshape(-1)
+    cnt = np.zeros(len(uniq), dtype=np.int64)
+    sum_abs = np.zeros(len(uniq), dtype=np.float64)
+    total = np.zeros(len(uniq), dtype=np.float64)
+    np.add.at(cnt, inv, 1)
+    np.add.at(sum_abs, inv, np.abs(val.astype(np.float64)))
+    np.add.at(total, inv, val.astype(np.float64))
+    out_imp = path + "_pair_importance"
+    with open(out_imp, "w") as f:
+        for k in np.lexsort((uniq[:, 1], uniq[:, 0], -sum_abs)):
+            f.write(f"{uniq[k, 0]} {uniq[k, 1]} {cnt[k]} {str(np.float32(sum_abs[k] / cnt[k]))} "
+                    f"{str(np.float32(total[k] / cnt[k]))}\n")
+    return [out_pairs, out_imp]
 
 
 def _occ_index(offs: np.ndarray, idx: np.ndarray) -> np.ndarray:
