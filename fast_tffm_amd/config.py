@@ -54,6 +54,10 @@ Extensions (new keys, all optional):
                 rank_cutoffs = <K>[,<K>...] (1 to 4 ascending integers in [1, 4096]: ``evaluate`` then also
                                 reports NDCG@K, recall@K and precision@K per group and writes <file>_rank; needs
                                 predict_group_files),
+                recommend_target_files = <files> (one integer per line, parallel to predict_files: the 0-based
+                                line of the context's held-out candidate in ``recommend --candidates FILE``, or
+                                -1 for none; ``recommend`` then also reports hit@K, ndcg@K, mrr@K and the mean
+                                place over all candidates and writes <file>_places; K: rank_cutoffs, else --top),
                 threshold_metrics = true|false (``evaluate`` then also reports the average precision, KS and
                                 the best F1 and writes <file>_thresholds; default false),
                 precision_targets = <p>[,<p>...] / recall_targets = <r>[,<r>...] (0 to 4 values in (0, 1] each:
@@ -165,6 +169,7 @@ class FMRunConfig:
     predict_files: list[str] = field(default_factory=list)
     predict_group_files: list[str] = field(default_factory=list)  # one group key per predict line (evaluate)
     rank_cutoffs: list[int] = field(default_factory=list)  # NDCG@K / recall@K / precision@K cutoffs (evaluate)
+    recommend_target_files: list[str] = field(default_factory=list)  # one held-out candidate per predict line
     validation_ap: bool = False          # report the average precision of the validation scores
     ap_tolerance: float | None = None    # stop when the validation average precision is >= this
     threshold_metrics: bool = False      # evaluate: average precision, KS, best F1 and <file>_thresholds
@@ -396,10 +401,15 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
         c.predict_group_files = _expand(pgf, base_dir)
         if len(c.predict_files) != len(c.predict_group_files):
             raise ConfigError("The numbers of predict files and predict group files do not match.")
+    rtf = read_list(PREDICT, "recommend_target_files", required=False)
+    if rtf is not None:
+        c.recommend_target_files = _expand(rtf, base_dir)
+        if len(c.predict_files) != len(c.recommend_target_files):
+            raise ConfigError("The numbers of predict files and recommend target files do not match.")
     rc = read_list(PREDICT, "rank_cutoffs", required=False)
     if rc is not None:
         c.rank_cutoffs = _cutoffs("rank_cutoffs", rc, 4)
-        if not c.predict_group_files:
+        if not c.predict_group_files and not c.recommend_target_files:
             raise ConfigError("rank_cutoffs needs predict_group_files.")
     c.threshold_metrics = opt(PREDICT, "threshold_metrics", to_bool, c.threshold_metrics)
     for key in ("precision_targets", "recall_targets"):

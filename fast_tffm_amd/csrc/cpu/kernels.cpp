@@ -14,6 +14,7 @@
 #include "../hash64.h"
 #include "../iso_hull.h"
 #include "../pairs_key.h"
+#include "../place_order.h"
 #include "../rank_table.h"
 #include "../score_key.h"
 #include "../threshold_rule.h"
@@ -977,6 +978,71 @@ void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q
       }
     }
   }
+}
+
+void place(long long nq, long long nc, int Kp, const float* Q, long long q_stride, const float* C,
+           long long c_stride, const float* qb, const float* cb, const int* target, int* counts, int threads) {
+  set_threads(threads);
+  std::vector<int> cols;  // pi(Kp)
+  topk::for_each_col(Kp, [&](int c) { cols.push_back(c); });
+#pragma omp parallel
+  {
+    std::vector<float> qv(cols.size());
+#pragma omp for schedule(dynamic, 1)
+    for (long long q = 0; q < nq; ++q) {
+      const int t = target[q];
+      int gt = 0, eq = 0;
+      if (t >= 0 && t < nc) {
+        const float* qr = Q + q * q_stride;
+        for (size_t i = 0; i < cols.size(); ++i) qv[i] = qr[cols[i]];
+        const auto score = [&](long long c) {
+          const float* cr = C + c * c_stride;
+          float dot = 0.f;
+          for (size_t i = 0; i < cols.size(); ++i) dot = std::fmaf(qv[i], cr[cols[i]], dot);
+          volatile float base = qb[q] + cb[c];  // (two additions as written, then + 0.f: topk's score)
+          volatile float sum = base + dot;
+          return sum + 0.f;
+        };
+        const float st = score(t);
+        for (long long c = 0; c < nc; ++c) {
+          const float s = score(c);
+          gt += s > st;
+          eq += s == st;
+        }
+      }
+      counts[2 * q] = gt;
+      counts[2 * q + 1] = eq;
+    }
+  }
+}
+
+bool place_metrics(long long n, const int* counts, const int* k, int nk, void* rec) {
+  if (!rank_cutoffs_ok(k, nk)) return false;
+  static const std::vector<double> tab = [] {
+    std::vector<double> t(2 * (kRankMaxCutoff + 1));
+    rank_dcg_table(t.data());
+    rank_harmonic_table(t.data() + kRankMaxCutoff + 1);
+    return t;
+  }();
+  const double *D = tab.data(), *H = D + kRankMaxCutoff + 1;
+  long long ranked = 0, ab = 0;
+  double sums[3 * kRankMaxCutoffs] = {};
+  for (long long q0 = 0; q0 < n; q0 += place::kMetricTile) {
+    double tile[3 * kRankMaxCutoffs] = {}, term[3 * kRankMaxCutoffs];
+    const long long q1 = std::min(n, q0 + place::kMetricTile);
+    for (long long q = q0; q < q1; ++q) {
+      const int gt = counts[2 * q], eq = counts[2 * q + 1];
+      if (gt < 0 || eq <= 0) continue;
+      ++ranked;
+      ab += place::terms(gt, eq, k, nk, D, H, term);
+      for (int c = 0; c < 3 * nk; ++c) tile[c] += term[c];
+    }
+    for (int c = 0; c < 3 * nk; ++c) sums[c] += tile[c];
+  }
+  std::memcpy(rec, &ranked, 8);
+  std::memcpy(static_cast<char*>(rec) + 8, &ab, 8);
+  std::memcpy(static_cast<char*>(rec) + 16, sums, sizeof(double) * 3 * nk);
+  return true;
 }
 
 void pairs(int B, const int* offsets, const int* rows, const float* vals, const void* v, long long v_stride, int Kp,

@@ -36,6 +36,17 @@ void explain(int B, const int* offsets, const int* rows, const float* vals, cons
 void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q_stride, const float* C,
           long long c_stride, const float* qb, const float* cb, int* idx, float* score, int threads);
 
+// The place of a held-out candidate among all candidates (hip/fm_place.hip: same definition, word for word):
+// with topk's score s, counts[q] = (#{c : s(q, c) > s(q, t)}, #{c : s(q, c) == s(q, t)}), t = target[q]; a target
+// outside [0, nc) leaves (0, 0): unranked.
+void place(long long nq, long long nc, int Kp, const float* Q, long long q_stride, const float* C,
+           long long c_stride, const float* qb, const float* cb, const int* target, int* counts, int threads);
+
+// The record of n (greater, equal) rows at the nk cutoffs k (../place_order.h; equal <= 0: unranked): rec[2 + 3 nk]
+// 64-bit words = ranked contexts, sum of a + b (int64), then hit, ndcg, mrr sums per cutoff (fp64), added per tile
+// of 1024 contexts in context order, the tiles in tile order, as the GPU does.  False: bad cutoffs.
+bool place_metrics(long long n, const int* counts, const int* k, int nk, void* rec);
+
 // The `top` strongest pairs of every example (hip/fm_pairs.hip: same definition, bit for bit): p_jl = (x_j x_l) *
 // fmaf chain over pi(Kp) for j < l, greatest |p| first, equal |p| by ascending (j, l); first / second = -1 and
 // value = 0 past the example's pairs, count = -1 for an example longer than pairs::kMaxN (../pairs_key.h).

@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../hash64.h"
+#include "../place_order.h"
 #include "../rank_table.h"
 #include "../topk_order.h"
 #include "bincsr.h"
@@ -377,6 +378,31 @@ PYBIND11_MODULE(_fm_cpu, m) {
       },
       py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("k"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
       py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("idx"), py::arg("score"), py::arg("threads"));
+
+  m.def(
+      "place_plan",
+      [](long long nq, long long nc) {
+        const fm::place::Plan p = fm::place::plan(nq, nc);
+        return py::make_tuple(p.slab, p.parts);
+      },
+      py::arg("nq"), py::arg("nc"));
+  m.def(
+      "place",
+      [](long long nq, long long nc, int Kp, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb, u64 cb,
+         u64 target, u64 counts, int threads) {
+        py::gil_scoped_release nogil;
+        fm::cpu::place(nq, nc, Kp, P<const float>(q), q_stride, P<const float>(c), c_stride, P<const float>(qb),
+                       P<const float>(cb), P<const int>(target), P<int>(counts), threads);
+      },
+      py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
+      py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("target"), py::arg("counts"), py::arg("threads"));
+  m.def(
+      "place_metrics",
+      [](long long n, u64 counts, const std::vector<int>& cutoffs, u64 rec) {
+        if (!fm::cpu::place_metrics(n, P<const int>(counts), cutoffs.data(), (int)cutoffs.size(), P<void>(rec)))
+          throw std::invalid_argument("place_metrics: 1 to 4 strictly ascending cutoffs in [1, 4096]");
+      },
+      py::arg("n"), py::arg("counts"), py::arg("cutoffs"), py::arg("rec"));
 
   m.def(
       "dedup",

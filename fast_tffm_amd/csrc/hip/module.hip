@@ -34,6 +34,7 @@ using u64 = std::uintptr_t;
 #include "isotonic.hip"
 #include "gauc.hip"
 #include "rank_metrics.hip"
+#include "fm_place.hip"
 #include "group_loss.hip"
 #include "group_pair.hip"
 #include "group_lambda.hip"
@@ -193,6 +194,44 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("k"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
       py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("ws"), py::arg("ws_bytes"), py::arg("idx"),
       py::arg("score"), py::arg("stream"));
+
+  m.def(
+      "place_plan",  // (slab, parts) of a place call: candidates per slab, partial counts per query (place_order.h)
+      [](long long nq, long long nc) {
+        const fm::place::Plan p = fm::place::plan(nq, nc);
+        return py::make_tuple(p.slab, p.parts);
+      },
+      py::arg("nq"), py::arg("nc"));
+  m.def("place_workspace_bytes", &fm::place_workspace_bytes, py::arg("nq"), py::arg("nc"), py::arg("nk"));
+  m.def("place_metrics_workspace_bytes", &fm::place_metrics_workspace_bytes, py::arg("n"), py::arg("nk"));
+  m.def(
+      "place",  // the held-out candidate's place (fm_place.hip): counts [nq, 2] int32 and the record [2 + 3 nk]
+      [](long long nq, long long nc, int Kp, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb, u64 cb,
+         u64 target, const std::vector<int>& cutoffs, u64 counts, u64 rec, u64 ws, size_t ws_bytes, u64 stream) {
+        fm::PlaceArgs a{};
+        a.nq = nq; a.nc = nc; a.Kp = Kp; a.Q = P<const float>(q); a.q_stride = q_stride; a.C = P<const float>(c);
+        a.c_stride = c_stride; a.qb = P<const float>(qb); a.cb = P<const float>(cb); a.target = P<const int>(target);
+        a.counts = P<int>(counts);
+        const int rc = fm::launch_place(a, cutoffs.data(), (int)cutoffs.size(), P<void>(rec), P<void>(ws), ws_bytes,
+                                        S(stream));
+        if (rc == -2) throw std::runtime_error("place: workspace too small");
+        if (rc == -7) throw std::invalid_argument("place: 1 to 4 strictly ascending cutoffs in [1, 4096]");
+        check(rc, "fm_place");
+      },
+      py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
+      py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("target"), py::arg("cutoffs"), py::arg("counts"),
+      py::arg("rec"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
+  m.def(
+      "place_metrics",  // the reduce pass of fm_place.hip alone: the record of n (greater, equal) rows
+      [](long long n, u64 counts, const std::vector<int>& cutoffs, u64 rec, u64 ws, size_t ws_bytes, u64 stream) {
+        const int rc = fm::launch_place_metrics(P<const int>(counts), n, cutoffs.data(), (int)cutoffs.size(),
+                                                P<void>(rec), P<void>(ws), ws_bytes, S(stream));
+        if (rc == -2) throw std::runtime_error("place_metrics: workspace too small");
+        if (rc == -7) throw std::invalid_argument("place_metrics: 1 to 4 strictly ascending cutoffs in [1, 4096]");
+        check(rc, "place_metrics");
+      },
+      py::arg("n"), py::arg("counts"), py::arg("cutoffs"), py::arg("rec"), py::arg("ws"), py::arg("ws_bytes"),
+      py::arg("stream"));
 
   m.def(
       "seg_index",

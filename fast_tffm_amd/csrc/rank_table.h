@@ -14,6 +14,13 @@ inline void rank_dcg_table(double* d /*[kRankMaxCutoff + 1]*/) {
   for (int j = 1; j <= kRankMaxCutoff; ++j) d[j] = d[j - 1] + 1.0 / std::log2(static_cast<double>(j) + 1.0);
 }
 
+// The harmonic table of the place metrics (hip/fm_place.hip and its CPU twin): H[r] = sum_{j <= r} 1 / j, the
+// reciprocal-rank mass of the places 1..r, built the same way.
+inline void rank_harmonic_table(double* h /*[kRankMaxCutoff + 1]*/) {
+  h[0] = 0.0;
+  for (int j = 1; j <= kRankMaxCutoff; ++j) h[j] = h[j - 1] + 1.0 / static_cast<double>(j);
+}
+
 // 1 to 4 strictly ascending cutoffs in [1, kRankMaxCutoff]
 inline bool rank_cutoffs_ok(const int* k, int nk) {
   if (!k || nk < 1 || nk > kRankMaxCutoffs) return false;

@@ -861,6 +861,17 @@ class FactorizationMachine:
         c_base = c_pred - self.gbias if self.gbias is not None else c_pred
         return K.fm_topk(q_prof, q_pred, c_prof, c_base, k, threads=self.cfg.threads)
 
+    @torch.no_grad()
+    def place(self, contexts: Batch, candidates, target: torch.Tensor, cutoffs=(10,)) -> "K.PlaceStats":
+        """The place of every context's held-out candidate among all candidates, by ``recommend``'s score:
+        ``target`` int32 ``[B]`` in ``[-1, candidates)`` (-1: no target), ``cutoffs`` 1 to 4 ascending integers in
+        [1, 4096]; the lazy record of ``K.fm_place`` (``counts``, ``hit`` / ``ndcg`` / ``mrr`` per cutoff,
+        ``mean_place``).  ``candidates``: a ``Batch`` or the ``(pred, S)`` pair of one, as in ``recommend``."""
+        c_pred, c_prof = self.profile(candidates) if isinstance(candidates, Batch) else candidates
+        q_pred, q_prof = self.profile(contexts)
+        c_base = c_pred - self.gbias if self.gbias is not None else c_pred
+        return K.fm_place(q_prof, q_pred, c_prof, c_base, target, cutoffs, threads=self.cfg.threads)
+
     def eval_loss(self, b: Batch) -> float:
         """Weighted mean loss of the configured type (reference valid_op, fm_model.py:317-333)."""
         fo = self.forward(b, loss=self.cfg.loss_type)

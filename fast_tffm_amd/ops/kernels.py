@@ -2076,6 +2076,174 @@ def fm_topk(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_
 
 
 # ---------------------------------------------------------------------------
+# the held-out candidate's place among all candidates (leave-one-out HR@k / NDCG@k / MRR)
+# ---------------------------------------------------------------------------
+class PlaceStats:
+    """The record of one ``fm_place`` / ``place_metrics`` call, on the op's device: ``counts`` (``[n, 2]`` int32,
+    ``(greater, equal)`` per context, zeros for an unranked one) and ``rec``, ``2 + 3 nk`` 64-bit words ``[ranked
+    contexts, sum of a + b over them (int64); per cutoff the sums of hit, ndcg, mrr (fp64)]`` with ``a = greater +
+    1 .. b = greater + equal`` the places the target holds.  The readers synchronise with the launch chain on the
+    GPU (``done``: the event behind it; None on the CPU and inside a graph capture)."""
+
+    __slots__ = ("_counts", "rec", "cutoffs", "n", "done")
+
+    def __init__(self, counts: torch.Tensor, rec: torch.Tensor, cutoffs: tuple, n: int,
+                 done: "torch.cuda.Event | None" = None):
+        self._counts, self.rec, self.cutoffs, self.n, self.done = counts, rec, cutoffs, n, done
+
+    def counts(self) -> torch.Tensor:
+        """The ``[n, 2]`` int32 ``(greater, equal)`` tensor on the op's device, once the chain has finished."""
+        if self.done is not None:
+            self.done.synchronize()
+        return self._counts
+
+    def stats(self) -> tuple:
+        """(ranked contexts, sum of a + b, the ``3 nk`` sums ``hit, ndcg, mrr`` per cutoff as floats) on the host."""
+        if self.done is not None:
+            self.done.synchronize()
+        r = self.rec.cpu()
+        i = r.tolist()
+        return i[0], i[1], r.view(torch.float64).tolist()[2:]
+
+    def ranked(self) -> int:
+        """Contexts with a target (the ones the means run over)."""
+        return self.stats()[0]
+
+    def _mean(self, k: int, which: int) -> float:
+        if isinstance(k, bool) or not isinstance(k, int):
+            raise ValueError(f"fm_place: a cutoff is an integer, got {k!r}")
+        if k not in self.cutoffs:
+            raise KeyError(f"fm_place: cutoff {k} is not one of this call's {self.cutoffs}")
+        ranked, _, sums = self.stats()
+        return sums[3 * self.cutoffs.index(k) + which] / ranked if ranked else float("nan")
+
+    def hit(self, k: int) -> float:
+        """Mean hit rate at ``k`` (the chance that the target is among the first ``k``); NaN without a ranked
+        context."""
+        return self._mean(k, 0)
+
+    def ndcg(self, k: int) -> float:
+        """Mean NDCG@k (one positive: the ideal DCG is 1); NaN as ``hit``."""
+        return self._mean(k, 1)
+
+    def mrr(self, k: int) -> float:
+        """Mean reciprocal rank, truncated at ``k``; NaN as ``hit``."""
+        return self._mean(k, 2)
+
+    def mean_place(self) -> float:
+        """Mean of ``(a + b) / 2`` over the ranked contexts (place 1 is best); NaN as ``hit``."""
+        ranked, ab, _ = self.stats()
+        return ab / (2 * ranked) if ranked else float("nan")
+
+
+def place_plan(nq: int, nc: int) -> tuple[int, int]:
+    """``(slab, parts)`` of an ``fm_place`` call on the GPU: the candidates per slab and the partial counts per
+    query (csrc/place_order.h; a pure function of the sizes, the same from the host module)."""
+    return tuple(native.cpu().place_plan(int(nq), int(nc)))
+
+
+def place_workspace(nq: int, nc: int, ncut: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of ``fm_place`` with ``ncut`` cutoffs (GPU): s_t, the ranked flags, the slabs' partial counts
+    and the metric tiles."""
+    return torch.empty(int(native.hip().place_workspace_bytes(int(nq), int(nc), int(ncut))), dtype=torch.uint8,
+                       device=device)
+
+
+def _place_cutoffs(cutoffs) -> tuple:
+    try:
+        return rank_cutoffs(cutoffs)
+    except ValueError as e:
+        raise ValueError(str(e).replace("rank_metrics", "fm_place")) from None
+
+
+def place_metrics(counts: torch.Tensor, cutoffs=(10,)) -> PlaceStats:
+    """The reduce pass of ``fm_place`` alone, on ``counts``' device: the record of ``[n, 2]`` int32 ``(greater,
+    equal)`` rows -- e.g. the counts several ranks gathered.  A row with ``equal <= 0`` is unranked.  fp64 sums per
+    tile of 1024 contexts in context order, the tiles in tile order: the same bits on both devices."""
+    ks = _place_cutoffs(cutoffs)
+    dev = counts.device
+    _check(counts.dim() == 2 and counts.shape[1] == 2, "counts: expected [n, 2]")
+    n = counts.shape[0]
+    _chk_vec(counts, torch.int32, 2 * n, "counts", dev)
+    _check(n < 2**31, "place_metrics: n must be below 2^31")
+    nw = 2 + 3 * len(ks)
+    if n == 0:  # (a host record: nothing is launched)
+        return PlaceStats(counts, torch.zeros(nw, dtype=torch.int64), ks, 0)
+    rec = torch.empty(nw, dtype=torch.int64, device=dev)
+    if _is_gpu(counts):
+        h = native.hip()
+        need = int(h.place_metrics_workspace_bytes(n, len(ks)))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+        h.place_metrics(n=n, counts=_p(counts), cutoffs=list(ks), rec=_p(rec), ws=_p(ws), ws_bytes=need,
+                        stream=_stream(counts))
+        done = None
+        if not torch.cuda.is_current_stream_capturing():
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(dev))
+        return PlaceStats(counts, rec, ks, n, done)
+    native.cpu().place_metrics(n=n, counts=_p(counts), cutoffs=list(ks), rec=_p(rec))
+    return PlaceStats(counts, rec, ks, n)
+
+
+def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_base: torch.Tensor,
+             target: torch.Tensor, cutoffs=(10,), *, counts: torch.Tensor | None = None,
+             ws: torch.Tensor | None = None, threads: int = 0) -> PlaceStats:
+    """The place of every query's held-out candidate among all candidates (hip/fm_place.hip), and the
+    leave-one-out metrics it implies.
+
+    The score is ``fm_topk``'s, bit for bit.  ``target``: int32 ``[nq]`` in ``[-1, nc)``; ``-1`` makes the query
+    unranked (all counters 0).  For a ranked query ``greater = #{c : s(q, c) > s_t}`` and ``equal = #{c : s(q, c)
+    == s_t}`` (the target counts: ``>= 1``), the target holds the places ``greater + 1 .. greater + equal``, and
+    ``hit@k`` / ``ndcg@k`` / ``mrr@k`` are the exact expectation under uniform tie-breaking over them, so they do
+    not depend on the order of the catalogue.  ``cutoffs``: 1 to 4 strictly ascending integers in [1, 4096].
+    Returns a lazy ``PlaceStats``.  GPU: the dense product on the matrix cores, the ``[nq, nc]`` scores never
+    reach memory; current stream, no host synchronisation, no atomics (``ws``: reusable ``place_workspace``;
+    capturable after one eager call on the device).  The target values are checked on the CPU and, with
+    FM_DEBUG_CHECKS=1, on the GPU; without it an out-of-range target is unranked there.  CPU: the same chain, word
+    for word the same counts.  ``nq == 0`` or ``nc == 0`` launches nothing: everything unranked.  Profiles are
+    expected to be finite."""
+    ks = _place_cutoffs(cutoffs)
+    dev = q_prof.device
+    nq, Kp, q_stride = _chk_profiles(q_prof, q_base, "q", dev)
+    nc, Kc, c_stride = _chk_profiles(c_prof, c_base, "c", dev)
+    _check(Kp == Kc, f"fm_place: profile widths differ ({Kp} and {Kc})")
+    _check(nc < 2**31 and nq < 2**31, "fm_place: nq and nc must be below 2^31")
+    _chk_vec(target, torch.int32, nq, "target", dev)
+    _check(target.numel() == nq, "target: one candidate (or -1) per query")
+    if nq and (not _is_gpu(target) or (_DEBUG and not torch.cuda.is_current_stream_capturing())):
+        _check(bool(target.min() >= -1) and bool(target.max() < nc), f"target: values must be in [-1, {nc})")
+    if counts is None:
+        counts = torch.empty((nq, 2), dtype=torch.int32, device=dev)
+    _chk_vec(counts, torch.int32, 2 * nq, "counts", dev)
+    _check(tuple(counts.shape) == (nq, 2), "counts: expected [nq, 2]")
+    nw = 2 + 3 * len(ks)
+    if nq == 0 or nc == 0:
+        _check(ws is None or _is_gpu(q_prof), "fm_place: the workspace is a GPU argument")
+        counts.zero_()
+        return PlaceStats(counts, torch.zeros(nw, dtype=torch.int64), ks, nq)
+    rec = torch.empty(nw, dtype=torch.int64, device=dev)
+    kw = dict(nq=nq, nc=nc, Kp=Kp, q=_p(q_prof), q_stride=q_stride, c=_p(c_prof), c_stride=c_stride,
+              qb=_p(q_base), cb=_p(c_base), target=_p(target), counts=_p(counts))
+    if _is_gpu(q_prof):
+        h = native.hip()
+        need = int(h.place_workspace_bytes(nq, nc, len(ks)))
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _chk_vec(ws, torch.uint8, need, "ws", dev)
+        _check(ws.data_ptr() % 8 == 0, "ws: must be 8-byte aligned")
+        h.place(cutoffs=list(ks), rec=_p(rec), ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(q_prof), **kw)
+        done = None
+        if not torch.cuda.is_current_stream_capturing():
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(dev))
+        return PlaceStats(counts, rec, ks, nq, done)
+    _check(ws is None, "fm_place: the workspace is a GPU argument")
+    native.cpu().place(threads=threads, **kw)
+    native.cpu().place_metrics(n=nq, counts=_p(counts), cutoffs=list(ks), rec=_p(rec))
+    return PlaceStats(counts, rec, ks, nq)
+
+
+# ---------------------------------------------------------------------------
 # sparse checkpoints: rows that differ from their initial state
 # ---------------------------------------------------------------------------
 def _bits_of(value: float, dtype: torch.dtype) -> int:

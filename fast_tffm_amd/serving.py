@@ -240,6 +240,21 @@ class ServingModel:
         return idx.cpu().numpy(), score.cpu().numpy()
 
 
+    def place(self, data_lines, candidates, targets, cutoffs=(10,)):
+        """The place of every context line's held-out candidate among all candidates, by ``recommend``'s score:
+        ``targets`` one candidate number (or -1: none) per line, ``cutoffs`` 1 to 4 ascending integers in [1, 4096].
+        Returns the lazy record of ``ops.kernels.fm_place`` (``counts()``, ``hit(k)``, ``ndcg(k)``, ``mrr(k)``,
+        ``mean_place()``).  ``candidates``: lines, or the ``index`` of them."""
+        from .ops import kernels as Kn
+
+        ci = candidates if isinstance(candidates, CandidateIndex) else self.index(candidates)
+        pred, prof, _ = self._profile(data_lines)
+        t = torch.as_tensor(np.asarray(targets, dtype=np.int64))
+        if t.numel() and (int(t.min()) < -1 or int(t.max()) >= len(ci)):
+            raise ValueError(f"place: targets must be in [-1, {len(ci)})")
+        return Kn.fm_place(prof, pred, ci.prof, ci.base, t.to(torch.int32).to(prof.device), cutoffs)
+
+
 class CandidateIndex:
     """Profiles of a candidate catalogue on the serving device (``ServingModel.index``)."""
 

@@ -561,7 +561,7 @@ class Trainer:
                                          "examples")
                     base = torch.from_numpy(base).to(self.device)
                 want_dl = (base,)
-            if c.rank_cutoffs:
+            if c.rank_cutoffs and c.predict_group_files:
                 loss, v_auc, st, rst, *tst = self.validation_report(mine.to(self.device), True, groups,
                                                                     rank_cutoffs=tuple(c.rank_cutoffs),
                                                                     thresholds=want_thr, delong=want_dl)
@@ -710,7 +710,13 @@ class Trainer:
         ``<file>_recommend``: line i holds up to ``top`` tokens ``c:score``, best first (equal scores by
         ascending c), c the 0-based line number of the candidate and the score that of the context's and the
         candidate's features taken together (``FactorizationMachine.recommend``).  Multi-rank runs deal the
-        contexts as ``predict`` does; every rank profiles all candidates."""
+        contexts as ``predict`` does; every rank profiles all candidates.
+
+        With ``[Predict] recommend_target_files`` (one integer per context line: the candidate held out for it, or
+        -1) it also prints ``recommend <file>: contexts N ranked R hit@K v ndcg@K v mrr@K v ... mean_place M`` --
+        the held-out candidate's place among all candidates (``FactorizationMachine.place``), K the
+        ``rank_cutoffs`` when set, else ``top`` -- and writes ``<file>_places``, one line ``target greater equal``
+        per context.  Multi-rank runs gather the counts and rank 0 reduces them (``K.place_metrics``)."""
         from .ops import kernels as K
 
         c = self.cfg
@@ -732,11 +738,16 @@ class Trainer:
             index = (torch.empty(0, dtype=torch.float32, device=self.device),
                      torch.empty((0, self.model.Kp), dtype=torch.float32, device=self.device))
         written = []
-        for path in c.predict_files:
+        cutoffs = tuple(c.rank_cutoffs) if c.rank_cutoffs else (top,)
+        for fi, path in enumerate(c.predict_files):
             b = load_file_batch([path], None, c.vocabulary_size, c.hash_feature_id, c.parse_threads)
             mine = (_take(b, torch.arange(self.rank, b.B, self.world)) if self.world > 1 else b).to(self.device)
             idx, score = self.model.recommend(mine, index, top)
             part = (idx.cpu().numpy(), score.cpu().numpy())
+            if c.recommend_target_files:
+                targets = _read_targets(c.recommend_target_files[fi], b.B, cands.B)
+                t_mine = torch.from_numpy(targets[self.rank::self.world].copy()).to(self.device)
+                part += (self.model.place(mine, index, t_mine, cutoffs).counts().cpu().numpy(),)
             parts = [part]
             if self.world > 1:
                 parts = [None] * self.world
@@ -745,17 +756,50 @@ class Trainer:
                 continue
             full_i = np.empty((b.B, top), dtype=np.int32)
             full_s = np.empty((b.B, top), dtype=np.float32)
-            for r, (i_r, s_r) in enumerate(parts):
-                full_i[r::self.world] = i_r
-                full_s[r::self.world] = s_r
+            for r, p_r in enumerate(parts):
+                full_i[r::self.world] = p_r[0]
+                full_s[r::self.world] = p_r[1]
             out = path + "_recommend"
             with open(out, "w") as f:
                 for i in range(b.B):
                     f.write(" ".join(f"{ci}:{str(np.float32(sc))}" for ci, sc in zip(full_i[i], full_s[i]) if ci >= 0)
                             + "\n")
             written.append(out)
+            if c.recommend_target_files:
+                counts = np.empty((b.B, 2), dtype=np.int32)
+                for r, p_r in enumerate(parts):
+                    counts[r::self.world] = p_r[2]
+                ps = K.place_metrics(torch.from_numpy(counts).to(self.device), cutoffs)
+                line = "recommend %s: contexts %d ranked %d" % (path, b.B, ps.ranked())
+                for kk in cutoffs:
+                    line += " hit@%d %.8f ndcg@%d %.8f mrr@%d %.8f" % (kk, ps.hit(kk), kk, ps.ndcg(kk), kk, ps.mrr(kk))
+                self.print(line + " mean_place %.8g" % ps.mean_place())
+                out = path + "_places"
+                with open(out, "w") as f:
+                    for t, (gt, eq) in zip(targets, counts):
+                        f.write(f"{t} {gt} {eq}\n")
+                written.append(out)
         self.print("Done. Recommendations saved to same directory as predict files")
         return written
+
+
+def _read_targets(path: str, lines: int, candidates: int) -> np.ndarray:
+    """The int32 targets of a ``recommend_target_files`` file: one integer in [-1, candidates) per context line."""
+    out = []
+    with open(path) as f:
+        for n, text in enumerate(f, 1):
+            try:
+                t = int(text.strip())
+            except ValueError:
+                t = None
+            if t is None or not -1 <= t < candidates:
+                raise ValueError(f"{path}, line {n}: expected a candidate line number in [-1, {candidates}), got "
+                                 f"{text.strip()!r}")
+            out.append(t)
+    if len(out) != lines:
+        raise ValueError(f"{path}, line {min(len(out), lines) + 1}: {len(out)} lines but the predict file has "
+                         f"{lines} contexts")
+    return np.array(out, dtype=np.int32)
 
 
 def _write_group_aucs(out: str, gi, recs: list) -> str:
