@@ -58,6 +58,9 @@ Extensions (new keys, all optional):
                                 line of the context's held-out candidate in ``recommend --candidates FILE``, or
                                 -1 for none; ``recommend`` then also reports hit@K, ndcg@K, mrr@K and the mean
                                 place over all candidates and writes <file>_places; K: rank_cutoffs, else --top),
+                recommend_seen_files = <files> (parallel to predict_files: line i holds the whitespace-separated
+                                0-based candidate lines context i has already seen, in any order, an empty line for
+                                none; ``recommend`` then leaves them out of <file>_recommend and of the places),
                 threshold_metrics = true|false (``evaluate`` then also reports the average precision, KS and
                                 the best F1 and writes <file>_thresholds; default false),
                 precision_targets = <p>[,<p>...] / recall_targets = <r>[,<r>...] (0 to 4 values in (0, 1] each:
@@ -170,6 +173,7 @@ class FMRunConfig:
     predict_group_files: list[str] = field(default_factory=list)  # one group key per predict line (evaluate)
     rank_cutoffs: list[int] = field(default_factory=list)  # NDCG@K / recall@K / precision@K cutoffs (evaluate)
     recommend_target_files: list[str] = field(default_factory=list)  # one held-out candidate per predict line
+    recommend_seen_files: list[str] = field(default_factory=list)    # the already-seen candidates of each predict line
     validation_ap: bool = False          # report the average precision of the validation scores
     ap_tolerance: float | None = None    # stop when the validation average precision is >= this
     threshold_metrics: bool = False      # evaluate: average precision, KS, best F1 and <file>_thresholds
@@ -406,7 +410,12 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
         c.recommend_target_files = _expand(rtf, base_dir)
         if len(c.predict_files) != len(c.recommend_target_files):
             raise ConfigError("The numbers of predict files and recommend target files do not match.")
-    rc = read_list(PREDICT, "rank_cutoffs", required=False)
+    rsf = read_list(PREDICT, "recommend_seen_files", required=False)
+    if rsf is not None:
+        c.recommend_seen_files = _expand(rsf, base_dir)
+        if len(c.predict_files) != len(c.recommend_seen_files):
+            raise ConfigError("The numbers of predict files and recommend seen files do not match.")
+    rc =read_list(PREDICT, "rank_cutoffs", required=False)
     if rc is not None:
         c.rank_cutoffs = _cutoffs("rank_cutoffs", rc, 4)
         if not c.predict_group_files and not c.recommend_target_files:

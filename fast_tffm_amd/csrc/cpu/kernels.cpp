@@ -934,7 +934,8 @@ void calib_apply(long long n, const float* scores, const float* x, const float* 
 }
 
 void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q_stride, const float* C,
-          long long c_stride, const float* qb, const float* cb, int* idx, float* score, int threads) {
+          long long c_stride, const float* qb, const float* cb, int* idx, float* score, int threads,
+          const int* seen_off, const int* seen_idx) {
   set_threads(threads);
   std::vector<int> cols;  // pi(Kp)
   topk::for_each_col(Kp, [&](int c) { cols.push_back(c); });
@@ -949,7 +950,12 @@ void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q
       const float* qr = Q + q * q_stride;
       for (size_t i = 0; i < cols.size(); ++i) qv[i] = qr[cols[i]];
       heap.clear();
+      // the query's seen list (ascending, as c is): sp walks it
+      int sp = seen_off ? seen_off[q] : 0;
+      const int se = seen_off ? seen_off[q + 1] : 0;
       for (long long c = 0; c < nc; ++c) {
+        while (sp < se && seen_idx[sp] < c) ++sp;
+        if (sp < se && seen_idx[sp] == c) continue;
         const float* cr = C + c * c_stride;
         float dot = 0.f;
         for (size_t i = 0; i < cols.size(); ++i) dot = std::fmaf(qv[i], cr[cols[i]], dot);
@@ -981,7 +987,8 @@ void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q
 }
 
 void place(long long nq, long long nc, int Kp, const float* Q, long long q_stride, const float* C,
-           long long c_stride, const float* qb, const float* cb, const int* target, int* counts, int threads) {
+           long long c_stride, const float* qb, const float* cb, const int* target, int* counts, int threads,
+           const int* seen_off, const int* seen_idx) {
   set_threads(threads);
   std::vector<int> cols;  // pi(Kp)
   topk::for_each_col(Kp, [&](int c) { cols.push_back(c); });
@@ -1004,7 +1011,11 @@ void place(long long nq, long long nc, int Kp, const float* Q, long long q_strid
           return sum + 0.f;
         };
         const float st = score(t);
+        int sp = seen_off ? seen_off[q] : 0;
+        const int se = seen_off ? seen_off[q + 1] : 0;
         for (long long c = 0; c < nc; ++c) {
+          while (sp < se && seen_idx[sp] < c) ++sp;
+          if (sp < se && seen_idx[sp] == c && c != t) continue;  // (the target competes even when it is listed)
           const float s = score(c);
           gt += s > st;
           eq += s == st;

@@ -365,8 +365,13 @@ inline int launch_place_metrics(const int* counts, long long n, const int* k, in
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
-// counts[nq, 2] and the record of nq >= 1 queries against nc >= 1 candidates.  Codes as launch_place_metrics.
-inline int launch_place(PlaceArgs a, const int* k, int nk, void* rec, void* ws, size_t ws_bytes, hipStream_t st) {
+// fm_seen.hip: takes every query's seen candidates (its target apart) out of counts again.
+inline int launch_place_seen(const PlaceArgs& a, const SeenArgs& sn, hipStream_t st);
+
+// counts[nq, 2] and the record of nq >= 1 queries against nc >= 1 candidates; `sn`: the lists of candidates that do
+// not compete (null: none, and nothing more is launched).  Codes as launch_place_metrics.
+inline int launch_place(PlaceArgs a, const int* k, int nk, void* rec, void* ws, size_t ws_bytes, hipStream_t st,
+                        const SeenArgs* sn = nullptr) {
   if (a.Kp < 4 || a.Kp > topk::kMaxKp || a.Kp % 4 || a.nq < 1 || a.nc < 1 || a.nc >= (1ll << 31) ||
       a.nq >= (1ll << 31) || !a.Q || !a.C || !a.qb || !a.cb || !a.target || !a.counts || !ws ||
       (reinterpret_cast<uintptr_t>(ws) & 7))
@@ -403,6 +408,8 @@ inline int launch_place(PlaceArgs a, const int* k, int nk, void* rec, void* ws, 
   hipLaunchKernelGGL(place_sum_kernel, dim3((unsigned)((sum_threads + kPlaceThreads - 1) / kPlaceThreads)),
                      dim3(kPlaceThreads), 0, st, a, L);
   if (hipGetLastError() != hipSuccess) return -3;
+  if (sn)
+    if (const int rc = launch_place_seen(a, *sn, st)) return rc;
   return launch_place_metrics(a.counts, a.nq, k, nk, rec, mbytes ? ws : nullptr, (size_t)mbytes, st);
 }
 

@@ -22,6 +22,8 @@
 // Phase 2, topk_merge_kernel: one wave per query streams its parts x k keys through the same threshold /
 // buffer selection and decodes the k best into idx / score (-1 / -inf where nc < k).
 // No host synchronisation, no allocation: the workspace comes from the caller (graph-capturable).
+// topk_slab_kernel<J, true> (fm_seen.hip) is the same pass with each query's already-seen candidates left out; the
+// plain instantiation takes no list and has no instruction for it.
 #include "fm_common.h"
 #include "../topk_order.h"
 
@@ -87,8 +89,33 @@ __device__ inline void topk_compact_rows(unsigned long long* buf, int cap, int k
   __syncthreads();
 }
 
-template <int J>  // column groups of 16: Kp in (16 (J - 1), 16 J]
-__global__ __launch_bounds__(kWave) void topk_slab_kernel(TopkArgs a, long long qtiles, int kcap) {
+// Per-query lists of candidates to leave out (fm_seen.hip): CSR, a query's indices strictly ascending in [0, nc).
+struct SeenArgs {
+  const int* off;   // [nq + 1]
+  const int* idx;   // [nnz]
+  int nnz;
+};
+
+// The first position p of [lo, hi) with idx[p] >= v (hi if none).  Reads stay inside [lo, hi) whatever the order.
+__device__ inline int seen_lower_bound(const int* idx, int lo, int hi, int v) {
+  while (lo < hi) {
+    const int mid = lo + ((hi - lo) >> 1);
+    if (idx[mid] < v) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+__device__ inline bool seen_contains(const int* idx, int lo, int hi, int v) {
+  const int p = seen_lower_bound(idx, lo, hi, v);
+  return p < hi && idx[p] == v;
+}
+
+// The lists as a kernel argument: nothing at all for the plain instantiation.
+template <bool SEEN> struct SeenOpt {};
+template <> struct SeenOpt<true> : SeenArgs {};
+
+// SEEN (launched by fm_seen.hip) leaves out every row's listed candidates; the plain instantiation has no code for it.
+template <int J, bool SEEN = false>  // column groups of 16: Kp in (16 (J - 1), 16 J]
+__global__ __launch_bounds__(kWave) void topk_slab_kernel(TopkArgs a, long long qtiles, int kcap, SeenOpt<SEEN> sn) {
   extern __shared__ __attribute__((aligned(16))) unsigned char topk_smem[];
   const int cap = 2 * kcap;
   unsigned long long* buf = reinterpret_cast<unsigned long long*>(topk_smem);       // [16][cap]
@@ -132,6 +159,20 @@ __global__ __launch_bounds__(kWave) void topk_slab_kernel(TopkArgs a, long long 
     qok[i] = q < a.nq;
     qbv[i] = qok[i] ? a.qb[q] : 0.f;
     thr[i] = 0ull;
+  }
+  // SEEN: the part [slo, shi) of each of this lane's rows' lists that lies inside the slab (the list's window
+  // clamped to [0, nnz]: a malformed list cannot lead a read out of bounds)
+  int slo[4] = {0, 0, 0, 0}, shi[4] = {0, 0, 0, 0};
+  if constexpr (SEEN) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      if (!qok[i]) continue;
+      const int o0 = sn.off[q0 + 4 * h + i], o1 = sn.off[q0 + 4 * h + i + 1];
+      const int b0 = o0 < 0 ? 0 : o0 > sn.nnz ? sn.nnz : o0;
+      const int e0 = o1 < b0 ? b0 : o1 > sn.nnz ? sn.nnz : o1;
+      slo[i] = seen_lower_bound(sn.idx, b0, e0, (int)c_begin);
+      shi[i] = seen_lower_bound(sn.idx, slo[i], e0, (int)c_end);
+    }
   }
 
   // B operands of the two candidate tiles at c0: rows c0 + r and c0 + 16 + r (clamped into the slab: loads
@@ -200,7 +241,21 @@ __global__ __launch_bounds__(kWave) void topk_slab_kernel(TopkArgs a, long long 
         win[i] = cok && qok[i] && key[i] > thr[i];
         any = any || win[i];
       }
-      if (__any(any)) {
+      bool some = __any(any);
+      if constexpr (SEEN) {
+        // Off the hot path: only a tile with a would-be winner looks at the lists.  A winner that its row has seen
+        // is cleared before the ballots, so it never reaches the buffer or a threshold.
+        if (some) {
+          any = false;
+#pragma unroll
+          for (int i = 0; i < 4; ++i) {
+            if (win[i] && slo[i] < shi[i] && seen_contains(sn.idx, slo[i], shi[i], (int)c32)) win[i] = false;
+            any = any || win[i];
+          }
+          some = __any(any);
+        }
+      }
+      if (some) {
         // every lane's 4 rows are different (4 h + i): all counts are read, then the keys and counts written
         int pos[4], newc[4];
         bool full = false;
@@ -281,22 +336,35 @@ inline long long topk_workspace_bytes(long long nq, long long nc, int k) {
   return nq * p.parts * k * (long long)sizeof(unsigned long long);
 }
 
-inline int launch_topk(TopkArgs a, hipStream_t stream) {
+// Checks a call's sizes and fills in its plan and phase 1's grid (shared with fm_seen.hip).  -1: bad arguments.
+inline int topk_prepare(TopkArgs& a, long long& qtiles, long long& blocks) {
   if (a.k < 1 || a.k > topk::kMaxK || a.Kp < 4 || a.Kp > topk::kMaxKp || a.Kp % 4 || a.nq < 0 || a.nc < 0 ||
       a.nc >= (1ll << 31))
     return -1;
-  if (a.nq == 0) return 0;
   const topk::Plan p = topk::plan(a.nq, a.nc, a.k);
   a.slab = p.slab;
   a.parts = p.parts;
-  const long long qtiles = (a.nq + topk::kTile - 1) / topk::kTile;
-  const long long blocks = qtiles * a.parts;
-  if (blocks >= (1ll << 31) || a.nq >= (1ll << 31)) return -1;
+  qtiles = (a.nq + topk::kTile - 1) / topk::kTile;
+  blocks = qtiles * a.parts;
+  return blocks >= (1ll << 31) || a.nq >= (1ll << 31) ? -1 : 0;
+}
+
+inline int launch_topk_merge(const TopkArgs& a, hipStream_t stream) {
+  const int kc2 = topk_kcap(a.k, kWave);
+  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)a.nq), dim3(kWave), topk_lds_bytes(1, kc2), stream, a, kc2);
+  return hipGetLastError() == hipSuccess ? 0 : -2;
+}
+
+inline int launch_topk(TopkArgs a, hipStream_t stream) {
+  long long qtiles = 0, blocks = 0;
+  if (topk_prepare(a, qtiles, blocks)) return -1;
+  if (a.nq == 0) return 0;
   const int kc1 = topk_kcap(a.k, 32);
   const size_t lds1 = topk_lds_bytes(topk::kTile, kc1);
 #define FM_TOPK_CASE(JJ)                                                                                       \
   case JJ:                                                                                                     \
-    hipLaunchKernelGGL((topk_slab_kernel<JJ>), dim3((unsigned)blocks), dim3(kWave), lds1, stream, a, qtiles, kc1); \
+    hipLaunchKernelGGL((topk_slab_kernel<JJ>), dim3((unsigned)blocks), dim3(kWave), lds1, stream, a, qtiles, kc1, \
+                       SeenOpt<false>{});                                                                      \
     break;
   switch (topk::groups(a.Kp)) {
     FM_TOPK_CASE(1) FM_TOPK_CASE(2) FM_TOPK_CASE(3) FM_TOPK_CASE(4) FM_TOPK_CASE(5) FM_TOPK_CASE(6)
@@ -305,9 +373,7 @@ inline int launch_topk(TopkArgs a, hipStream_t stream) {
     default: return -1;
   }
 #undef FM_TOPK_CASE
-  const int kc2 = topk_kcap(a.k, kWave);
-  hipLaunchKernelGGL(topk_merge_kernel, dim3((unsigned)a.nq), dim3(kWave), topk_lds_bytes(1, kc2), stream, a, kc2);
-  return hipGetLastError() == hipSuccess ? 0 : -2;
+  return launch_topk_merge(a, stream);
 }
 
 }  // namespace fm

@@ -35,6 +35,7 @@ using u64 = std::uintptr_t;
 #include "gauc.hip"
 #include "rank_metrics.hip"
 #include "fm_place.hip"
+#include "fm_seen.hip"
 #include "group_loss.hip"
 #include "group_pair.hip"
 #include "group_lambda.hip"
@@ -183,17 +184,22 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
   m.def(
       "topk",  // the k best candidates of every query from profiles (fm_topk.hip): idx [nq, k], score [nq, k]
       [](long long nq, long long nc, int Kp, int k, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb,
-         u64 cb, u64 ws, size_t ws_bytes, u64 idx, u64 score, u64 stream) {
+         u64 cb, u64 ws, size_t ws_bytes, u64 idx, u64 score, u64 stream, u64 seen_off, u64 seen_idx, int seen_nnz) {
         if ((long long)ws_bytes < fm::topk_workspace_bytes(nq, nc, k)) throw std::runtime_error("topk: workspace too small");
         fm::TopkArgs a{};
         a.nq = nq; a.nc = nc; a.Kp = Kp; a.k = k; a.Q = P<const float>(q); a.q_stride = q_stride;
         a.C = P<const float>(c); a.c_stride = c_stride; a.qb = P<const float>(qb); a.cb = P<const float>(cb);
         a.ws = P<unsigned long long>(ws); a.idx = P<int>(idx); a.score = P<float>(score);
-        check(fm::launch_topk(a, S(stream)), "fm_topk");
+        if (seen_off) {  // (fm_seen.hip; no list: the plain kernels with the plain arguments)
+          const fm::SeenArgs sn{P<const int>(seen_off), P<const int>(seen_idx), seen_nnz};
+          check(fm::launch_topk_seen(a, sn, S(stream)), "fm_topk (seen)");
+        } else {
+          check(fm::launch_topk(a, S(stream)), "fm_topk");
+        }
       },
       py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("k"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
       py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("ws"), py::arg("ws_bytes"), py::arg("idx"),
-      py::arg("score"), py::arg("stream"));
+      py::arg("score"), py::arg("stream"), py::arg("seen_off") = 0, py::arg("seen_idx") = 0, py::arg("seen_nnz") = 0);
 
   m.def(
       "place_plan",  // (slab, parts) of a place call: candidates per slab, partial counts per query (place_order.h)
@@ -207,20 +213,23 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
   m.def(
       "place",  // the held-out candidate's place (fm_place.hip): counts [nq, 2] int32 and the record [2 + 3 nk]
       [](long long nq, long long nc, int Kp, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb, u64 cb,
-         u64 target, const std::vector<int>& cutoffs, u64 counts, u64 rec, u64 ws, size_t ws_bytes, u64 stream) {
+         u64 target, const std::vector<int>& cutoffs, u64 counts, u64 rec, u64 ws, size_t ws_bytes, u64 stream,
+         u64 seen_off, u64 seen_idx, int seen_nnz) {
         fm::PlaceArgs a{};
         a.nq = nq; a.nc = nc; a.Kp = Kp; a.Q = P<const float>(q); a.q_stride = q_stride; a.C = P<const float>(c);
         a.c_stride = c_stride; a.qb = P<const float>(qb); a.cb = P<const float>(cb); a.target = P<const int>(target);
         a.counts = P<int>(counts);
+        const fm::SeenArgs sn{P<const int>(seen_off), P<const int>(seen_idx), seen_nnz};
         const int rc = fm::launch_place(a, cutoffs.data(), (int)cutoffs.size(), P<void>(rec), P<void>(ws), ws_bytes,
-                                        S(stream));
+                                        S(stream), seen_off ? &sn : nullptr);
         if (rc == -2) throw std::runtime_error("place: workspace too small");
         if (rc == -7) throw std::invalid_argument("place: 1 to 4 strictly ascending cutoffs in [1, 4096]");
         check(rc, "fm_place");
       },
       py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
       py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("target"), py::arg("cutoffs"), py::arg("counts"),
-      py::arg("rec"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
+      py::arg("rec"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"), py::arg("seen_off") = 0,
+      py::arg("seen_idx") = 0, py::arg("seen_nnz") = 0);
   m.def(
       "place_metrics",  // the reduce pass of fm_place.hip alone: the record of n (greater, equal) rows
       [](long long n, u64 counts, const std::vector<int>& cutoffs, u64 rec, u64 ws, size_t ws_bytes, u64 stream) {

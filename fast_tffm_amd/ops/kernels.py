@@ -2033,9 +2033,47 @@ def _chk_profiles(t: torch.Tensor, base: torch.Tensor, name: str, dev: torch.dev
     return n, Kp, stride
 
 
+def seen_lists(lists, nc: int, device) -> tuple[torch.Tensor, torch.Tensor]:
+    """The ``seen`` argument of ``fm_topk`` / ``fm_place`` from a sequence of per-context sequences of candidate
+    numbers: ``(seen_offsets int32 [nq + 1], seen_idx int32 [nnz])`` on ``device``, every context's indices sorted
+    and without duplicates.  A value outside ``[0, nc)`` raises ``ValueError`` naming the context."""
+    off, idx = [0], []
+    for q, row in enumerate(lists):
+        r = sorted({int(c) for c in row})
+        if r and (r[0] < 0 or r[-1] >= nc):
+            raise ValueError(f"seen_lists: context {q}: candidate {r[0] if r[0] < 0 else r[-1]} is outside [0, {nc})")
+        idx += r
+        off.append(len(idx))
+    _check(len(idx) < 2**31, "seen_lists: the lists must hold fewer than 2^31 entries")
+    return (torch.tensor(off, dtype=torch.int32, device=device), torch.tensor(idx, dtype=torch.int32, device=device))
+
+
+def _chk_seen(seen, nq: int, nc: int, dev: torch.device, op: str) -> dict:
+    """Validate the ``seen`` pair of ``op`` and return the native call's keyword arguments (none without lists).
+    The values are checked on the CPU and, with FM_DEBUG_CHECKS=1 and outside a capture, on the GPU."""
+    if seen is None:
+        return {}
+    _check(isinstance(seen, (tuple, list)) and len(seen) == 2, f"{op}: seen is the pair (seen_offsets, seen_idx)")
+    off, idx = seen
+    _chk_vec(off, torch.int32, nq + 1, "seen_offsets", dev)
+    _chk_vec(idx, torch.int32, None, "seen_idx", dev)
+    _check(off.numel() == nq + 1, f"seen_offsets: expected {nq + 1} entries (nq + 1), got {off.numel()}")
+    nnz = idx.numel()
+    if not _is_gpu(off) or (_DEBUG and not torch.cuda.is_current_stream_capturing()):
+        _check(int(off[0]) == 0 and int(off[-1]) == nnz, f"seen_offsets: must run from 0 to {nnz} (seen_idx's length)")
+        _check(bool((off[1:] >= off[:-1]).all()), "seen_offsets: must not decrease")
+        if nnz:
+            _check(bool(idx.min() >= 0) and bool(idx.max() < nc), f"seen_idx: values must be in [0, {nc})")
+            up = idx[1:] > idx[:-1]
+            starts = off[1:-1].long()
+            up[starts[(starts >= 1) & (starts < nnz)] - 1] = True   # (a new context may start lower)
+            _check(bool(up.all()), "seen_idx: a context's indices must be strictly ascending")
+    return dict(seen_off=_p(off), seen_idx=_p(idx), seen_nnz=nnz)
+
+
 def fm_topk(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_base: torch.Tensor, k: int, *,
             idx: torch.Tensor | None = None, score: torch.Tensor | None = None, ws: torch.Tensor | None = None,
-            threads: int = 0) -> tuple[torch.Tensor, torch.Tensor]:
+            threads: int = 0, seen=None) -> tuple[torch.Tensor, torch.Tensor]:
     """The ``k`` best candidates of every query from FM profiles (hip/fm_topk.hip; the reference only scores).
 
     ``s(q, c) = ((q_base[q] + c_base[c]) + dot) + 0`` with ``dot`` the fp32 fmaf chain of ``q_prof[q]`` and
@@ -2043,13 +2081,22 @@ def fm_topk(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_
     score [nq, k] fp32)``: greater score first, equal scores by ascending candidate, ``-1`` / ``-inf`` where
     there are fewer than ``k`` candidates.  Exact fp32 on the matrix cores (gfx950's fp32-input MFMA), bitwise
     reproducible, and bit for bit the same on the CPU.  GPU: current stream, no host synchronisation (``ws``:
-    reusable ``topk_workspace``).  Profiles are expected to be finite."""
+    reusable ``topk_workspace``).  Profiles are expected to be finite.
+
+    ``seen``: ``(seen_offsets int32 [nq + 1], seen_idx int32 [nnz])`` on the profiles' device (``seen_lists``
+    builds it), per query the candidates to leave out, strictly ascending in ``[0, nc)``: row q then holds the
+    ``k`` best of the others, ``-1`` / ``-inf`` where fewer remain (hip/fm_seen.hip: the filtered slab pass; a
+    membership search only for a key that beats its row's threshold).  The lists are checked on the CPU and, with
+    FM_DEBUG_CHECKS=1, on the GPU; without the check a malformed list gives unspecified membership.  A list that
+    covers most of the catalogue is correct but slow: every candidate then pays a search.  ``None`` launches the
+    plain kernels."""
     dev = q_prof.device
     _check(isinstance(k, int) and 1 <= k <= TOPK_MAX_K, f"fm_topk: k must be in 1..{TOPK_MAX_K}, got {k}")
     nq, Kp, q_stride = _chk_profiles(q_prof, q_base, "q", dev)
     nc, Kc, c_stride = _chk_profiles(c_prof, c_base, "c", dev)
     _check(Kp == Kc, f"fm_topk: profile widths differ ({Kp} and {Kc})")
     _check(nc < 2**31 and nq < 2**31, "fm_topk: nq and nc must be below 2^31")
+    skw = _chk_seen(seen, nq, nc, dev, "fm_topk")
     if idx is None:
         idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
     if score is None:
@@ -2068,10 +2115,11 @@ def fm_topk(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
         _chk_vec(ws, torch.uint8, need, "ws", dev)
         _check(ws.data_ptr() % 8 == 0, "ws: must be 8-byte aligned")
-        h.topk(ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(q_prof), **kw)
+        h.topk(ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(q_prof), **kw, **skw)
     else:
         _check(ws is None, "fm_topk: the workspace is a GPU argument")
-        native.cpu().topk(threads=threads, **kw)
+        skw.pop("seen_nnz", None)
+        native.cpu().topk(threads=threads, **kw, **skw)
     return idx, score
 
 
@@ -2187,7 +2235,7 @@ def place_metrics(counts: torch.Tensor, cutoffs=(10,)) -> PlaceStats:
 
 def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_base: torch.Tensor,
              target: torch.Tensor, cutoffs=(10,), *, counts: torch.Tensor | None = None,
-             ws: torch.Tensor | None = None, threads: int = 0) -> PlaceStats:
+             ws: torch.Tensor | None = None, threads: int = 0, seen=None) -> PlaceStats:
     """The place of every query's held-out candidate among all candidates (hip/fm_place.hip), and the
     leave-one-out metrics it implies.
 
@@ -2201,7 +2249,13 @@ def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c
     capturable after one eager call on the device).  The target values are checked on the CPU and, with
     FM_DEBUG_CHECKS=1, on the GPU; without it an out-of-range target is unranked there.  CPU: the same chain, word
     for word the same counts.  ``nq == 0`` or ``nc == 0`` launches nothing: everything unranked.  Profiles are
-    expected to be finite."""
+    expected to be finite.
+
+    ``seen``: the lists of ``fm_topk`` (same layout, same checks).  A query's listed candidates do not compete:
+    ``greater`` and ``equal`` count the ``c`` outside ``E_q \\ {target}`` -- the query's own target always competes,
+    so ``equal >= 1`` still holds -- and a query with target ``-1`` stays all zeros.  GPU: one more small launch
+    after the count pass (hip/fm_seen.hip) scores the listed candidates with the same fmaf chain and subtracts
+    their counts; the workspace is the same.  ``None`` launches the plain kernels."""
     ks = _place_cutoffs(cutoffs)
     dev = q_prof.device
     nq, Kp, q_stride = _chk_profiles(q_prof, q_base, "q", dev)
@@ -2212,6 +2266,7 @@ def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c
     _check(target.numel() == nq, "target: one candidate (or -1) per query")
     if nq and (not _is_gpu(target) or (_DEBUG and not torch.cuda.is_current_stream_capturing())):
         _check(bool(target.min() >= -1) and bool(target.max() < nc), f"target: values must be in [-1, {nc})")
+    skw = _chk_seen(seen, nq, nc, dev, "fm_place")
     if counts is None:
         counts = torch.empty((nq, 2), dtype=torch.int32, device=dev)
     _chk_vec(counts, torch.int32, 2 * nq, "counts", dev)
@@ -2231,14 +2286,15 @@ def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
         _chk_vec(ws, torch.uint8, need, "ws", dev)
         _check(ws.data_ptr() % 8 == 0, "ws: must be 8-byte aligned")
-        h.place(cutoffs=list(ks), rec=_p(rec), ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(q_prof), **kw)
+        h.place(cutoffs=list(ks), rec=_p(rec), ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(q_prof), **kw, **skw)
         done = None
         if not torch.cuda.is_current_stream_capturing():
             done = torch.cuda.Event()
             done.record(torch.cuda.current_stream(dev))
         return PlaceStats(counts, rec, ks, nq, done)
     _check(ws is None, "fm_place: the workspace is a GPU argument")
-    native.cpu().place(threads=threads, **kw)
+    skw.pop("seen_nnz", None)
+    native.cpu().place(threads=threads, **kw, **skw)
     native.cpu().place_metrics(n=nq, counts=_p(counts), cutoffs=list(ks), rec=_p(rec))
     return PlaceStats(counts, rec, ks, nq)
 

@@ -716,7 +716,13 @@ class Trainer:
         -1) it also prints ``recommend <file>: contexts N ranked R hit@K v ndcg@K v mrr@K v ... mean_place M`` --
         the held-out candidate's place among all candidates (``FactorizationMachine.place``), K the
         ``rank_cutoffs`` when set, else ``top`` -- and writes ``<file>_places``, one line ``target greater equal``
-        per context.  Multi-rank runs gather the counts and rank 0 reduces them (``K.place_metrics``)."""
+        per context.  Multi-rank runs gather the counts and rank 0 reduces them (``K.place_metrics``).
+
+        With ``[Predict] recommend_seen_files`` (line i: the candidate line numbers context i has already seen, in
+        any order, an empty line for none) ``<file>_recommend`` leaves each context's list out, the places are
+        taken among the candidates it has not seen (its own target always competes), and the printed line ends
+        with `` seen E``, the file's list entries without duplicates.  Multi-rank runs deal the lists with their
+        contexts."""
         from .ops import kernels as K
 
         c = self.cfg
@@ -742,12 +748,17 @@ class Trainer:
         for fi, path in enumerate(c.predict_files):
             b = load_file_batch([path], None, c.vocabulary_size, c.hash_feature_id, c.parse_threads)
             mine = (_take(b, torch.arange(self.rank, b.B, self.world)) if self.world > 1 else b).to(self.device)
-            idx, score = self.model.recommend(mine, index, top)
+            seen, tail = None, ""
+            if c.recommend_seen_files:
+                lists = _read_seen(c.recommend_seen_files[fi], b.B, cands.B)
+                seen = K.seen_lists(lists[self.rank::self.world], cands.B, self.device)
+                tail = " seen %d" % sum(len(s) for s in lists)
+            idx, score = self.model.recommend(mine, index, top, seen=seen)
             part = (idx.cpu().numpy(), score.cpu().numpy())
             if c.recommend_target_files:
                 targets = _read_targets(c.recommend_target_files[fi], b.B, cands.B)
                 t_mine = torch.from_numpy(targets[self.rank::self.world].copy()).to(self.device)
-                part += (self.model.place(mine, index, t_mine, cutoffs).counts().cpu().numpy(),)
+                part += (self.model.place(mine, index, t_mine, cutoffs, seen=seen).counts().cpu().numpy(),)
             parts = [part]
             if self.world > 1:
                 parts = [None] * self.world
@@ -773,7 +784,7 @@ class Trainer:
                 line = "recommend %s: contexts %d ranked %d" % (path, b.B, ps.ranked())
                 for kk in cutoffs:
                     line += " hit@%d %.8f ndcg@%d %.8f mrr@%d %.8f" % (kk, ps.hit(kk), kk, ps.ndcg(kk), kk, ps.mrr(kk))
-                self.print(line + " mean_place %.8g" % ps.mean_place())
+                self.print(line + " mean_place %.8g" % ps.mean_place() + tail)
                 out = path + "_places"
                 with open(out, "w") as f:
                     for t, (gt, eq) in zip(targets, counts):
@@ -800,6 +811,26 @@ def _read_targets(path: str, lines: int, candidates: int) -> np.ndarray:
         raise ValueError(f"{path}, line {min(len(out), lines) + 1}: {len(out)} lines but the predict file has "
                          f"{lines} contexts")
     return np.array(out, dtype=np.int32)
+
+
+def _read_seen(path: str, lines: int, candidates: int) -> list:
+    """The lists of a ``recommend_seen_files`` file: per context line the sorted distinct candidate line numbers
+    in [0, candidates) it names (whitespace-separated, any order; an empty line: none)."""
+    out = []
+    with open(path) as f:
+        for n, text in enumerate(f, 1):
+            try:
+                row = sorted({int(tok) for tok in text.split()})
+            except ValueError:
+                row = None
+            if row is None or (row and not 0 <= row[0] <= row[-1] < candidates):
+                raise ValueError(f"{path}, line {n}: expected candidate line numbers in [0, {candidates}), got "
+                                 f"{text.strip()!r}")
+            out.append(row)
+    if len(out) != lines:
+        raise ValueError(f"{path}, line {min(len(out), lines) + 1}: {len(out)} lines but the predict file has "
+                         f"{lines} contexts")
+    return out
 
 
 def _write_group_aucs(out: str, gi, recs: list) -> str:
