@@ -7,7 +7,7 @@
 //   c(r) = 1 / log2(r + 1) for r <= K (every r when K = 0), else 0;  IDCG = sum_r G_(r) c(r), gains descending;
 //   for every pair G_i > G_j:  delta_ij = (G_i - G_j) |c(r_i) - c(r_j)| / IDCG   (a constant: no gradient through r)
 //   L_g = sum delta_ij softplus(s_j - s_i),   dL/ds_i -= delta_ij sigma(s_j - s_i),   dL/ds_j += the same
-//   softplus(d) = max(d, 0) + log1p(t), sigma(d) = 1 / (1 + t) or t / (1 + t), t = exp(-|d|)   (group_pair.hip's)
+//   softplus(d) = max(d, 0) + log1p(t), sigma(d) = 1 / (1 + t) or t / (1 + t), t = exp(-|d|)   (group_walk.hip's)
 //   A group with IDCG == 0, a group of one and an excluded example add exactly 0 and get exactly 0, whatever their
 //   scores hold: no arithmetic touches them.  A pair counts only when one of its two places is <= K.
 //
@@ -25,13 +25,12 @@
 //   head:   per tile of the score order: score, gain (fp32) and discount (fp64) per position (the only gathers of
 //           the pair stage) and the tile's column span: the union over its rows of what each needs -- a row of
 //           place <= K its whole group, a row of place > K only the group's head [first, min(first + K, end));
-//   pair:   grid (row tile) x (column slab).  The span is cut into kGmChunk-aligned chunks dealt to kGmSlabs
-//           slabs of equally many; a slab stages its chunks (score, gain, discount) through LDS; a thread keeps
-//           its 4 rows' (s, G, c, column range) in registers and walks, per staged chunk, only its row's own
-//           range, columns ascending, skipping columns of equal gain.  Per pair delta' = |dG| |dc|; the sigma term
-//           goes to the row's "up" sum when the row has the larger gain (with the softplus term to a third sum),
-//           else to its "down" sum.  One fp64 partial set per (slab, position); a workgroup whose slab is empty
-//           returns.  With K = 10 a tile wholly in a big group's tail has a one-chunk span and one live slab, the
+//   pair:   group_walk.hip's pair stage, grid (row tile) x (column slab): a slab stages its chunks (score, gain,
+//           discount) through LDS; a thread keeps its 4 rows' (s, G, c, column range) in registers and walks, per
+//           staged chunk, only its row's own range, columns ascending, skipping columns of equal gain.  Per pair
+//           delta' = |dG| |dc|; the sigma term goes to the row's "up" sum when the row has the larger gain (with
+//           the softplus term to a third sum), else to its "down" sum.  One fp64 partial set per (slab,
+//           position).  With K = 10 a tile wholly in a big group's tail has a one-chunk span and one live slab, the
 //           tile that holds the head fans out over all slabs: about sum_g 2 n_g min(K, n_g) pairs (K = 0: n_g^2);
 //   grad:   every position adds its slab partials in slab order, takes down - up once and divides by IDCG once;
 //           dpred[example] = fp32(grad_scale ...); the rows' softplus sums / IDCG go to the tile's loss partial
@@ -39,15 +38,13 @@
 //   final:  gl_final_kernel: the tile partials in tile order -> fp32 loss.
 // Everything is fp64 (exp, log1p, log2 and the divisions too); every sum adds non-negative terms in an order fixed
 // by n, K and the group structure; dpred and the loss are rounded once: bitwise the same run to run.  Every pair
-// is evaluated from both of its rows.  (Included by module.hip after group_pair.hip: GlArgs, GlPos / gl_positions,
-// gl_tile_reduce, the carry and final kernels, gauc_bits_for, score_key, the radix sort and WsCursor come before.)
+// is evaluated from both of its rows.  (Included by module.hip after group_pair.hip: GlArgs, gl_bind, GlPos /
+// gl_positions, gl_tile_reduce, the carry and final kernels, gauc_bits_for, score_key, the radix sort and WsCursor,
+// and group_walk.hip's geometry, GwSpan and logistic pair term come before.)
 #include "fm_common.h"
 
 namespace fm {
 
-constexpr int kGmChunk = 128;        // columns staged per step
-static_assert(kGmChunk <= kBlock, "one thread stages one column");
-constexpr int kGmSlabs = 16;         // column slabs of a row tile's span
 constexpr int kGmMaxCutoff = 4096;   // K = 0 (no truncation) or 1..kGmMaxCutoff
 
 struct GmLayout {
@@ -76,9 +73,9 @@ static GmLayout gm_layout(int n) {
   l.sgain = c.take(4 * N);
   l.sc = c.take(8 * N);
   l.gred = c.take(8 * N);
-  l.pup = c.take(8 * (size_t)kGmSlabs * N);
-  l.pdn = c.take(8 * (size_t)kGmSlabs * N);
-  l.psp = c.take(8 * (size_t)kGmSlabs * N);
+  l.pup = c.take(8 * (size_t)kGwSlabs * N);
+  l.pdn = c.take(8 * (size_t)kGwSlabs * N);
+  l.psp = c.take(8 * (size_t)kGwSlabs * N);
   l.tflag = c.take(4 * nt);
   l.tv = c.take(8 * nt);
   l.fv = c.take(8 * nt);
@@ -102,9 +99,9 @@ struct GmArgs {
   const int* sort_err;  // the error word of the sort that made it
   float* sgain;         // [n] gain of every position of the score order
   double* sc;           // [n] its discount
-  double* pup;          // [kGmSlabs, n] sigma sums over the columns of smaller gain
-  double* pdn;          // [kGmSlabs, n] ... of larger gain
-  double* psp;          // [kGmSlabs, n] softplus sums over the columns of smaller gain
+  double* pup;          // [kGwSlabs, n] sigma sums over the columns of smaller gain
+  double* pdn;          // [kGwSlabs, n] ... of larger gain
+  double* psp;          // [kGwSlabs, n] softplus sums over the columns of smaller gain
   int* tlo;             // [ntiles] the tile's column span
   int* thi;
 };
@@ -125,16 +122,6 @@ __device__ inline bool gm_row_group(const GlArgs& g, int j, int& fi, int& e) {
 // The columns a row of the given place needs: its whole group, or the group's head when it lies below the cutoff.
 __device__ inline int gm_row_end(int fi, int e, int place, int K) {
   return (K == 0 || place <= K) ? e : min(fi + K, e);
-}
-
-// The chunks [cb, ce) of slab s of the span [lo, hi); false: none.
-__device__ inline bool gm_slab(int lo, int hi, int s, int& cb, int& ce) {
-  if (hi <= lo) return false;
-  const int c0 = lo / kGmChunk, c1 = (hi + kGmChunk - 1) / kGmChunk;
-  const int per = (c1 - c0 + kGmSlabs - 1) / kGmSlabs;
-  cb = c0 + s * per;
-  ce = min(c1, cb + per);
-  return cb < ce;
 }
 
 __device__ inline void gm_report_sort(const int* sort_err) {
@@ -197,13 +184,9 @@ __global__ __launch_bounds__(kBlock) void gm_ideal_kernel(GmArgs a) {
 
 // ---- head -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void gm_head_kernel(GmArgs a) {
-  __shared__ int slo, shi;
+  __shared__ GwSpan span;
   const GlArgs& g = a.g;
-  if (threadIdx.x == 0) {
-    slo = g.n;
-    shi = 0;
-  }
-  __syncthreads();
+  gw_span_open(span, g.n);
   gm_report_sort(a.sort_err);
   const int j0 = blockIdx.x * kGlTile + threadIdx.x * kGlItems;
   int lo = g.n, hi = 0;
@@ -228,27 +211,21 @@ __global__ __launch_bounds__(kBlock) void gm_head_kernel(GmArgs a) {
     a.sgain[j] = gain;
     a.sc[j] = c;
   }
-  if (lo < hi) {
-    atomicMin(&slo, lo);
-    atomicMax(&shi, hi);
-  }
+  gw_span_add(span, lo, hi);
   __syncthreads();
-  if (threadIdx.x == 0) {
-    a.tlo[blockIdx.x] = min(slo, shi);
-    a.thi[blockIdx.x] = shi;
-  }
+  gw_span_close(span, a.tlo, a.thi);
 }
 
 // ---- pair -------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(kBlock) void gm_pair_kernel(GmArgs a) {
-  __shared__ float shs[kGmChunk];
-  __shared__ float shg[kGmChunk];
-  __shared__ double shc[kGmChunk];
+  __shared__ float shs[kGwChunk];
+  __shared__ float shg[kGwChunk];
+  __shared__ double shc[kGwChunk];
   const GlArgs& g = a.g;
   const int n = g.n;
   const int lo = max(a.tlo[blockIdx.x], 0), hi = min(a.thi[blockIdx.x], n);
   int cb, ce;
-  if (!gm_slab(lo, hi, blockIdx.y, cb, ce)) return;
+  if (!gw_slab(lo, hi, blockIdx.y, cb, ce)) return;
   const int j0 = blockIdx.x * kGlTile + threadIdx.x * kGlItems;
   int f[kGlItems], e[kGlItems];
   double rs[kGlItems], rg[kGlItems], rc[kGlItems], up[kGlItems], dn[kGlItems], sp[kGlItems];
@@ -267,8 +244,8 @@ __global__ __launch_bounds__(kBlock) void gm_pair_kernel(GmArgs a) {
     rc[q] = a.sc[j];
   }
   for (int c = cb; c < ce; ++c) {
-    const int clo = c * kGmChunk;
-    if (threadIdx.x < kGmChunk) {
+    const int clo = c * kGwChunk;
+    if (threadIdx.x < kGwChunk) {
       const int col = clo + (int)threadIdx.x;
       const bool ok = col < n;
       shs[threadIdx.x] = ok ? g.ss[col] : 0.f;
@@ -278,7 +255,7 @@ __global__ __launch_bounds__(kBlock) void gm_pair_kernel(GmArgs a) {
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < kGlItems; ++q) {
-      const int c0 = max(f[q], clo) - clo, c1 = min(e[q], clo + kGmChunk) - clo;
+      const int c0 = max(f[q], clo) - clo, c1 = min(e[q], clo + kGwChunk) - clo;
       for (int k = c0; k < c1; ++k) {
         const double gk = (double)shg[k];
         if (gk == rg[q]) continue;
@@ -287,10 +264,10 @@ __global__ __launch_bounds__(kBlock) void gm_pair_kernel(GmArgs a) {
         const double sk = (double)shs[k];
         const double d = larger ? sk - rs[q] : rs[q] - sk;  // s of the smaller gain - s of the larger
         const double t = exp(-fabs(d));
-        const double sg = dl * ((d >= 0.0 ? 1.0 : t) / (1.0 + t));
+        const double sg = dl * gw_sigma(d, t);
         if (larger) {
           up[q] += sg;
-          sp[q] += dl * (fmax(d, 0.0) + log1p(t));
+          sp[q] += dl * gw_softplus(d, t);
         } else {
           dn[q] += sg;
         }
@@ -327,9 +304,9 @@ __global__ __launch_bounds__(kBlock) void gm_grad_kernel(GmArgs a) {
     int fi, en;
     if (gm_row_group(g, j, fi, en)) {
       double up = 0.0, dn = 0.0, sp = 0.0;
-      for (int s = 0; s < kGmSlabs; ++s) {
+      for (int s = 0; s < kGwSlabs; ++s) {
         int cb, ce;
-        if (!gm_slab(lo, hi, s, cb, ce)) continue;
+        if (!gw_slab(lo, hi, s, cb, ce)) continue;
         up += a.pup[(size_t)s * n + j];
         dn += a.pdn[(size_t)s * n + j];
         sp += a.psp[(size_t)s * n + j];
@@ -351,32 +328,14 @@ __global__ __launch_bounds__(kBlock) void gm_grad_kernel(GmArgs a) {
 int launch_group_lambda(const void* plan_ws, size_t plan_bytes, int n, const float* scores, const float* labels,
                         int cutoff, double grad_scale, float* dpred, float* loss, void* ws, size_t ws_bytes,
                         hipStream_t st) {
-  if (n < 1 || (unsigned)n > kOsCnt || !plan_ws || !scores || !labels || !dpred || !loss || !ws) return -1;
-  if ((reinterpret_cast<uintptr_t>(ws) & 15) || (reinterpret_cast<uintptr_t>(plan_ws) & 15)) return -1;
+  if (!gl_args_ok(plan_ws, n, scores, labels, dpred, loss, ws)) return -1;
   if (cutoff < 0 || cutoff > kGmMaxCutoff) return -9;
-  const GlLayout pl = gl_layout(n);
   const GmLayout l = gm_layout(n);
-  if (ws_bytes < l.total || plan_bytes < pl.total) return -2;
-  const char* pb = static_cast<const char*>(plan_ws);
+  if (ws_bytes < l.total || plan_bytes < gl_layout(n).total) return -2;
   char* b = static_cast<char*>(ws);
   GmArgs a{};
   GlArgs& g = a.g;
-  g.n = n;
-  g.ntiles = l.ntiles;
-  g.grad_scale = grad_scale;
-  g.scores = scores;
-  g.labels = labels;
-  g.sidx = reinterpret_cast<const int*>(pb + pl.sidx);
-  g.first = reinterpret_cast<const int*>(pb + pl.first);
-  g.end = reinterpret_cast<const int*>(pb + pl.end);
-  g.ss = reinterpret_cast<float*>(b + l.ss);
-  g.gred = reinterpret_cast<double*>(b + l.gred);
-  g.tflag = reinterpret_cast<int*>(b + l.tflag);
-  g.tv = reinterpret_cast<double*>(b + l.tv);
-  g.fv = reinterpret_cast<double*>(b + l.fv);
-  g.lpart = reinterpret_cast<double*>(b + l.lpart);
-  g.dpred = dpred;
-  g.loss = loss;
+  gl_bind(g, l, ws, plan_ws, n, scores, labels, nullptr, grad_scale, dpred, loss);
   a.cutoff = cutoff;
   a.sgain = reinterpret_cast<float*>(b + l.sgain);
   a.sc = reinterpret_cast<double*>(b + l.sc);
@@ -413,7 +372,7 @@ int launch_group_lambda(const void* plan_ws, size_t plan_bytes, int n, const flo
     }
   }
   hipLaunchKernelGGL(gm_head_kernel, tiles, blk, 0, st, a);
-  hipLaunchKernelGGL(gm_pair_kernel, dim3(l.ntiles, kGmSlabs), blk, 0, st, a);
+  hipLaunchKernelGGL(gm_pair_kernel, dim3(l.ntiles, kGwSlabs), blk, 0, st, a);
   hipLaunchKernelGGL(gm_grad_kernel, tiles, blk, 0, st, a);
   hipLaunchKernelGGL(gl_final_kernel, dim3(1), one, 0, st, g);
   return (int)hipGetLastError();

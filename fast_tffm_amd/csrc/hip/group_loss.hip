@@ -439,39 +439,56 @@ __global__ __launch_bounds__(kAucBaseThreads) void gl_final_kernel(GlArgs a) {
   if (threadIdx.x == 0) *a.loss = (float)tot;
 }
 
+// What every score half (the softmax here, group_pair.hip, group_lambda.hip) asks of its arguments: n in [1, 2^30),
+// no null pointer but weights, both workspaces 16-byte aligned.
+inline bool gl_args_ok(const void* plan_ws, int n, const float* scores, const float* labels, const float* dpred,
+                       const float* loss, const void* ws) {
+  if (n < 1 || (unsigned)n > kOsCnt || !plan_ws || !scores || !labels || !dpred || !loss || !ws) return false;
+  return !((reinterpret_cast<uintptr_t>(ws) & 15) || (reinterpret_cast<uintptr_t>(plan_ws) & 15));
+}
+
+// Points g at the call's inputs and outputs, the plan in plan_ws and, by the score half's own layout l (GlLayout,
+// GpLayout, GmLayout), at the arrays of ws that every score half has: ss, gred, tflag, tv, fv, lpart.
+template <typename L>
+inline void gl_bind(GlArgs& g, const L& l, void* ws, const void* plan_ws, int n, const float* scores,
+                    const float* labels, const float* weights, double grad_scale, float* dpred, float* loss) {
+  const GlLayout pl = gl_layout(n);
+  const char* pb = static_cast<const char*>(plan_ws);
+  char* b = static_cast<char*>(ws);
+  g.n = n;
+  g.ntiles = l.ntiles;
+  g.grad_scale = grad_scale;
+  g.scores = scores;
+  g.labels = labels;
+  g.weights = weights;
+  g.sidx = reinterpret_cast<const int*>(pb + pl.sidx);
+  g.first = reinterpret_cast<const int*>(pb + pl.first);
+  g.end = reinterpret_cast<const int*>(pb + pl.end);
+  g.ss = reinterpret_cast<float*>(b + l.ss);
+  g.gred = reinterpret_cast<double*>(b + l.gred);
+  g.tflag = reinterpret_cast<int*>(b + l.tflag);
+  g.tv = reinterpret_cast<double*>(b + l.tv);
+  g.fv = reinterpret_cast<double*>(b + l.fv);
+  g.lpart = reinterpret_cast<double*>(b + l.lpart);
+  g.dpred = dpred;
+  g.loss = loss;
+}
+
 // The loss of the n >= 1 examples planned into plan_ws: dpred[n] (example order) and loss[1], asynchronously on st;
 // ws (the plan's own workspace, or another one of the same size) holds the intermediates.  0 or a hip error code;
 // -1: bad arguments; -2: a workspace is too small.
 int launch_group_softmax(const void* plan_ws, size_t plan_bytes, int n, const float* scores, const float* labels,
                          const float* weights, double grad_scale, float* dpred, float* loss, void* ws, size_t ws_bytes,
                          hipStream_t st) {
-  if (n < 1 || (unsigned)n > kOsCnt || !plan_ws || !scores || !labels || !dpred || !loss || !ws) return -1;
-  if ((reinterpret_cast<uintptr_t>(ws) & 15) || (reinterpret_cast<uintptr_t>(plan_ws) & 15)) return -1;
+  if (!gl_args_ok(plan_ws, n, scores, labels, dpred, loss, ws)) return -1;
   const GlLayout l = gl_layout(n);
   if (ws_bytes < l.total || plan_bytes < l.total) return -2;
-  const char* pb = static_cast<const char*>(plan_ws);
   char* b = static_cast<char*>(ws);
   GlArgs a{};
-  a.n = n;
-  a.ntiles = l.ntiles;
-  a.grad_scale = grad_scale;
-  a.scores = scores;
-  a.labels = labels;
-  a.weights = weights;
-  a.sidx = reinterpret_cast<const int*>(pb + l.sidx);
-  a.first = reinterpret_cast<const int*>(pb + l.first);
-  a.end = reinterpret_cast<const int*>(pb + l.end);
-  a.ss = reinterpret_cast<float*>(b + l.ss);
+  gl_bind(a, l, ws, plan_ws, n, scores, labels, weights, grad_scale, dpred, loss);
   a.sa = reinterpret_cast<double*>(b + l.sa);
   a.sz = reinterpret_cast<double*>(b + l.sz);
   a.gm = reinterpret_cast<double*>(b + l.gm);
-  a.gred = reinterpret_cast<double*>(b + l.gred);
-  a.tflag = reinterpret_cast<int*>(b + l.tflag);
-  a.tv = reinterpret_cast<double*>(b + l.tv);
-  a.fv = reinterpret_cast<double*>(b + l.fv);
-  a.lpart = reinterpret_cast<double*>(b + l.lpart);
-  a.dpred = dpred;
-  a.loss = loss;
   const dim3 tiles(l.ntiles), blk(kBlock), one(kAucBaseThreads);
   hipLaunchKernelGGL(gl_max_kernel, tiles, blk, 0, st, a);
   if (l.ntiles > 1) hipLaunchKernelGGL(gl_max_carry_kernel, dim3(1), one, 0, st, a);  // (one tile: nothing is open)

@@ -16,11 +16,10 @@
 //           position (the only gathers through the sorted index), P and N per group by the segmented tile
 //           reduction, and the tile's column span [lo, hi): the union of the ranges of the groups that touch it;
 //   carry:  gl_sum_carry_kernel, two channels: the groups that cross tiles;
-//   pair:   grid (row tile) x (column slab).  The span is cut into kGpChunk-aligned column chunks, the chunks
-//           into kGpSlabs slabs of equally many; a slab stages its chunks (score, signed weight) through LDS and
-//           every thread walks, per row it owns, the part of the chunk inside the row's group range, columns
-//           ascending, and evaluates the columns of the opposite class.  One fp64 partial per (slab, position):
-//           the sigma sum, for a positive row the softplus sum too.  A workgroup whose slab is empty returns;
+//   pair:   group_walk.hip's pair stage, grid (row tile) x (column slab): a slab stages its chunks (score, signed
+//           weight) through LDS and every thread walks, per row it owns, the part of the chunk inside the row's
+//           group range, columns ascending, and evaluates the columns of the opposite class.  One fp64 partial
+//           per (slab, position): the sigma sum, for a positive row the softplus sum too;
 //   grad:   every position adds its slab partials in slab order; dpred[example] = fp32(grad_scale (-+) c |w| sum);
 //           a positive row adds c p_i (its softplus sum) to the tile's loss partial (thread order, block scan);
 //   final:  gl_final_kernel: the tile partials in tile order -> fp32 loss.
@@ -28,15 +27,12 @@
 // whole batch is 128 row tiles x 16 slabs (of 64 chunks each) at B = 131072.  d = (double)s_j - (double)s_i; exp,
 // log1p, the division and every sum are fp64; every sum adds non-negative terms in an order fixed by n and the group structure; dpred
 // and the loss are rounded once: bitwise the same run to run.  Every pair is evaluated from both of its rows.
-// (Included by module.hip after group_loss.hip: GlArgs, GlPos / gl_positions, gl_tile_reduce, the carry and final
-// kernels, auc_block_scan and WsCursor are defined before it.)
+// (Included by module.hip after group_walk.hip: GlArgs, gl_bind, GlPos / gl_positions, gl_tile_reduce, the carry and
+// final kernels and WsCursor -- group_loss.hip's -- and the walk's geometry, GwSpan, and the logistic pair term are
+// defined before it.)
 #include "fm_common.h"
 
 namespace fm {
-
-constexpr int kGpChunk = 128;      // columns staged per step (a row tile's own 1024 columns: 8 or 9 slabs of one)
-static_assert(kGpChunk <= kBlock, "one thread stages one column");
-constexpr int kGpSlabs = 16;       // column slabs of a row tile's span
 
 struct GpLayout {
   size_t ss, cw, gred, psig, psp, tflag, tv, fv, lpart, tlo, thi, total;
@@ -52,8 +48,8 @@ static GpLayout gp_layout(int n) {
   l.ss = c.take(4 * N);
   l.cw = c.take(8 * N);
   l.gred = c.take(8 * 2 * N);
-  l.psig = c.take(8 * (size_t)kGpSlabs * N);
-  l.psp = c.take(8 * (size_t)kGpSlabs * N);
+  l.psig = c.take(8 * (size_t)kGwSlabs * N);
+  l.psp = c.take(8 * (size_t)kGwSlabs * N);
   l.tflag = c.take(4 * nt);
   l.tv = c.take(8 * 2 * nt);
   l.fv = c.take(8 * 2 * nt);
@@ -73,32 +69,18 @@ size_t group_pair_workspace_bytes(long long n) {
 struct GpArgs {
   GlArgs g;        // n, ntiles, grad_scale, inputs, the plan, ss, gred [2, n] (P, N), tflag, tv, fv, lpart, outputs
   double* cw;      // [n] signed class weight of every sorted position: +p, -q, 0
-  double* psig;    // [kGpSlabs, n] sigma sums
-  double* psp;     // [kGpSlabs, n] softplus sums (positive rows)
+  double* psig;    // [kGwSlabs, n] sigma sums
+  double* psp;     // [kGwSlabs, n] softplus sums (positive rows)
   int* tlo;        // [ntiles] the tile's column span
   int* thi;
 };
 
-// The chunks [cb, ce) of slab s of the span [lo, hi); false: none.
-__device__ inline bool gp_slab(int lo, int hi, int s, int& cb, int& ce) {
-  if (hi <= lo) return false;
-  const int c0 = lo / kGpChunk, c1 = (hi + kGpChunk - 1) / kGpChunk;
-  const int per = (c1 - c0 + kGpSlabs - 1) / kGpSlabs;
-  cb = c0 + s * per;
-  ce = min(c1, cb + per);
-  return cb < ce;
-}
-
 __global__ __launch_bounds__(kBlock) void gp_class_kernel(GpArgs a) {
   __shared__ int shf[kWavesPerBlock];
   __shared__ double shv[kWavesPerBlock];
-  __shared__ int slo, shi;
+  __shared__ GwSpan span;
   const GlArgs& g = a.g;
-  if (threadIdx.x == 0) {
-    slo = g.n;
-    shi = 0;
-  }
-  __syncthreads();
+  gw_span_open(span, g.n);
   const int j0 = blockIdx.x * kGlTile + threadIdx.x * kGlItems;
   GlPos p;
   gl_positions(g, j0, p);
@@ -128,27 +110,21 @@ __global__ __launch_bounds__(kBlock) void gp_class_kernel(GpArgs a) {
     g.ss[j] = sc;
     a.cw[j] = cw;
   }
-  if (lo < hi) {
-    atomicMin(&slo, lo);
-    atomicMax(&shi, hi);
-  }
+  gw_span_add(span, lo, hi);
   const size_t N = (size_t)g.n, nt = (size_t)g.ntiles;
   gl_tile_reduce<GlAdd>(p, vp, g.gred, g.tv, g.fv, g.tflag, shf, shv);
   gl_tile_reduce<GlAdd>(p, vn, g.gred + N, g.tv + nt, g.fv + nt, nullptr, shf, shv);
-  if (threadIdx.x == 0) {  // (the reductions' barriers lie between the atomics and this read)
-    a.tlo[blockIdx.x] = min(slo, shi);
-    a.thi[blockIdx.x] = shi;
-  }
+  gw_span_close(span, a.tlo, a.thi);  // (the reductions' barriers lie between the adds and this read)
 }
 
 __global__ __launch_bounds__(kBlock) void gp_pair_kernel(GpArgs a) {
-  __shared__ float shs[kGpChunk];
-  __shared__ double shw[kGpChunk];
+  __shared__ float shs[kGwChunk];
+  __shared__ double shw[kGwChunk];
   const GlArgs& g = a.g;
   const int n = g.n;
   const int lo = max(a.tlo[blockIdx.x], 0), hi = min(a.thi[blockIdx.x], n);
   int cb, ce;
-  if (!gp_slab(lo, hi, blockIdx.y, cb, ce)) return;
+  if (!gw_slab(lo, hi, blockIdx.y, cb, ce)) return;
   const int j0 = blockIdx.x * kGlTile + threadIdx.x * kGlItems;
   int f[kGlItems], e[kGlItems];
   double rs[kGlItems], rw[kGlItems], sig[kGlItems], sp[kGlItems];
@@ -169,8 +145,8 @@ __global__ __launch_bounds__(kBlock) void gp_pair_kernel(GpArgs a) {
     rw[q] = w;
   }
   for (int c = cb; c < ce; ++c) {
-    const int clo = c * kGpChunk;
-    if (threadIdx.x < kGpChunk) {
+    const int clo = c * kGwChunk;
+    if (threadIdx.x < kGwChunk) {
       const int col = clo + (int)threadIdx.x;
       const bool ok = col < n;
       shs[threadIdx.x] = ok ? g.ss[col] : 0.f;
@@ -179,7 +155,7 @@ __global__ __launch_bounds__(kBlock) void gp_pair_kernel(GpArgs a) {
     __syncthreads();
 #pragma unroll
     for (int q = 0; q < kGlItems; ++q) {
-      const int c0 = max(f[q], clo) - clo, c1 = min(e[q], clo + kGpChunk) - clo;
+      const int c0 = max(f[q], clo) - clo, c1 = min(e[q], clo + kGwChunk) - clo;
       const bool pos = rw[q] > 0.0;
       for (int k = c0; k < c1; ++k) {
         const double w = shw[k];
@@ -188,8 +164,8 @@ __global__ __launch_bounds__(kBlock) void gp_pair_kernel(GpArgs a) {
         const double d = pos ? sc - rs[q] : rs[q] - sc;  // s_neg - s_pos
         const double t = exp(-fabs(d));
         const double aw = fabs(w);
-        sig[q] += aw * ((d >= 0.0 ? 1.0 : t) / (1.0 + t));
-        if (pos) sp[q] += aw * (fmax(d, 0.0) + log1p(t));
+        sig[q] += aw * gw_sigma(d, t);
+        if (pos) sp[q] += aw * gw_softplus(d, t);
       }
     }
     __syncthreads();
@@ -224,9 +200,9 @@ __global__ __launch_bounds__(kBlock) void gp_grad_kernel(GpArgs a) {
       const double P = g.gred[fi], N = g.gred[(size_t)n + fi];
       if (P > 0.0 && N > 0.0) {
         double sig = 0.0, sp = 0.0;
-        for (int s = 0; s < kGpSlabs; ++s) {
+        for (int s = 0; s < kGwSlabs; ++s) {
           int cb, ce;
-          if (!gp_slab(lo, hi, s, cb, ce)) continue;
+          if (!gw_slab(lo, hi, s, cb, ce)) continue;
           sig += a.psig[(size_t)s * n + j];
           if (w > 0.0) sp += a.psp[(size_t)s * n + j];
         }
@@ -248,32 +224,13 @@ __global__ __launch_bounds__(kBlock) void gp_grad_kernel(GpArgs a) {
 int launch_group_pairwise(const void* plan_ws, size_t plan_bytes, int n, const float* scores, const float* labels,
                           const float* weights, double grad_scale, float* dpred, float* loss, void* ws, size_t ws_bytes,
                           hipStream_t st) {
-  if (n < 1 || (unsigned)n > kOsCnt || !plan_ws || !scores || !labels || !dpred || !loss || !ws) return -1;
-  if ((reinterpret_cast<uintptr_t>(ws) & 15) || (reinterpret_cast<uintptr_t>(plan_ws) & 15)) return -1;
-  const GlLayout pl = gl_layout(n);
+  if (!gl_args_ok(plan_ws, n, scores, labels, dpred, loss, ws)) return -1;
   const GpLayout l = gp_layout(n);
-  if (ws_bytes < l.total || plan_bytes < pl.total) return -2;
-  const char* pb = static_cast<const char*>(plan_ws);
+  if (ws_bytes < l.total || plan_bytes < gl_layout(n).total) return -2;
   char* b = static_cast<char*>(ws);
   GpArgs a{};
   GlArgs& g = a.g;
-  g.n = n;
-  g.ntiles = l.ntiles;
-  g.grad_scale = grad_scale;
-  g.scores = scores;
-  g.labels = labels;
-  g.weights = weights;
-  g.sidx = reinterpret_cast<const int*>(pb + pl.sidx);
-  g.first = reinterpret_cast<const int*>(pb + pl.first);
-  g.end = reinterpret_cast<const int*>(pb + pl.end);
-  g.ss = reinterpret_cast<float*>(b + l.ss);
-  g.gred = reinterpret_cast<double*>(b + l.gred);
-  g.tflag = reinterpret_cast<int*>(b + l.tflag);
-  g.tv = reinterpret_cast<double*>(b + l.tv);
-  g.fv = reinterpret_cast<double*>(b + l.fv);
-  g.lpart = reinterpret_cast<double*>(b + l.lpart);
-  g.dpred = dpred;
-  g.loss = loss;
+  gl_bind(g, l, ws, plan_ws, n, scores, labels, weights, grad_scale, dpred, loss);
   a.cw = reinterpret_cast<double*>(b + l.cw);
   a.psig = reinterpret_cast<double*>(b + l.psig);
   a.psp = reinterpret_cast<double*>(b + l.psp);
@@ -282,7 +239,7 @@ int launch_group_pairwise(const void* plan_ws, size_t plan_bytes, int n, const f
   const dim3 tiles(l.ntiles), blk(kBlock), one(kAucBaseThreads);
   hipLaunchKernelGGL(gp_class_kernel, tiles, blk, 0, st, a);
   if (l.ntiles > 1) hipLaunchKernelGGL(gl_sum_carry_kernel, dim3(2), one, 0, st, g);  // (one tile: nothing is open)
-  hipLaunchKernelGGL(gp_pair_kernel, dim3(l.ntiles, kGpSlabs), blk, 0, st, a);
+  hipLaunchKernelGGL(gp_pair_kernel, dim3(l.ntiles, kGwSlabs), blk, 0, st, a);
   hipLaunchKernelGGL(gp_grad_kernel, tiles, blk, 0, st, a);
   hipLaunchKernelGGL(gl_final_kernel, dim3(1), one, 0, st, g);
   return (int)hipGetLastError();

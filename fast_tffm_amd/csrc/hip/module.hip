@@ -37,6 +37,7 @@ using u64 = std::uintptr_t;
 #include "fm_place.hip"
 #include "fm_seen.hip"
 #include "group_loss.hip"
+#include "group_walk.hip"
 #include "group_pair.hip"
 #include "group_lambda.hip"
 #include "shard.hip"
@@ -576,8 +577,8 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       py::arg("grad_scale"), py::arg("dpred"), py::arg("loss"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
 
   m.attr("GROUP_PAIR_ROWS") = fm::kGlTile;      // sorted positions per row tile of the pairwise loss
-  m.attr("GROUP_PAIR_CHUNK") = fm::kGpChunk;    // columns per chunk (chunks start at multiples of it)
-  m.attr("GROUP_PAIR_SLABS") = fm::kGpSlabs;    // column slabs of a row tile's span
+  m.attr("GROUP_PAIR_CHUNK") = fm::kGwChunk;  // columns per chunk (chunks start at multiples of it)
+  m.attr("GROUP_PAIR_SLABS") = fm::kGwSlabs;  // column slabs of a row tile's span
   m.def(
       "group_pair_workspace_bytes",
       [](long long n) {
@@ -600,8 +601,8 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       py::arg("grad_scale"), py::arg("dpred"), py::arg("loss"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
 
   m.attr("GROUP_LAMBDA_ROWS") = fm::kGlTile;          // sorted positions per row tile of the LambdaRank loss
-  m.attr("GROUP_LAMBDA_CHUNK") = fm::kGmChunk;        // columns per chunk (chunks start at multiples of it)
-  m.attr("GROUP_LAMBDA_SLABS") = fm::kGmSlabs;        // column slabs of a row tile's span
+  m.attr("GROUP_LAMBDA_CHUNK") = fm::kGwChunk;      // columns per chunk (chunks start at multiples of it)
+  m.attr("GROUP_LAMBDA_SLABS") = fm::kGwSlabs;      // column slabs of a row tile's span
   m.attr("GROUP_LAMBDA_MAX_CUTOFF") = fm::kGmMaxCutoff;
   m.def(
       "group_lambda_workspace_bytes",

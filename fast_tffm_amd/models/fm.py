@@ -10,8 +10,8 @@ Here the step is an explicit pipeline of native kernels, no autograd graph:
                         (loss_type = rank_softmax: fwd scores | dedup + group plan -> listwise loss -> bwd;
                         the plan half of ops.kernels.group_softmax_loss depends on the batch alone and travels
                         with the batch's dedup, the score half sits between forward and backward;
-                        loss_type = rank_pairwise: the same plan, ops.kernels.group_pairwise_loss in that slot;
-                        loss_type = rank_lambda: the same plan, ops.kernels.group_lambda_loss in that slot)
+                        loss_type = rank_pairwise, rank_lambda: the same plan, their score half in that slot --
+                        ops.kernels.group_loss picks it by the loss_type)
   shard (row-sharded):  dedup -> a2a(ids) -> owner gather -> a2a(rows) -> fwd
                         -> bwd(emit grads) -> a2a(grads) -> owner sum+optimizer
   dp    (replicated):   local fwd/bwd(emit) -> all_gather(ids, grads) -> every
@@ -91,14 +91,13 @@ class _Workspace:
     """Per-step buffers, grown on demand and then reused (no per-step allocation)."""
 
     def __init__(self, device: torch.device, Kp: int, CH: int, r1_dtype: torch.dtype = torch.float32,
-                 group_loss: bool = False, pair_loss: bool = False, lambda_loss: bool = False):
+                 loss_type: str = "mse"):
         self.device, self.Kp, self.CH, self.r1_dtype = device, Kp, CH, r1_dtype
         self.cap_b = self.cap_n = 0
-        self.group = _GroupBufs() if group_loss else None  # rank losses only: the plan of the unplanned step
-        self.pair_ws = None   # pairwise loss only (GPU): the workspace of its score half
-        self._pair_loss = pair_loss
-        self.lambda_ws = None  # LambdaRank loss only (GPU): the workspace of its score half
-        self._lambda_loss = lambda_loss
+        self.loss_type = loss_type
+        # rank losses only: the plan of the unplanned step, and (GPU; not rank_softmax) the score half's own workspace
+        self.group = _GroupBufs() if loss_type in K.GROUP_LOSSES else None
+        self.loss_ws = None
 
     def ensure(self, B: int, nnz: int) -> None:
         dev, Kp = self.device, self.Kp
@@ -110,10 +109,7 @@ class _Workspace:
             self.cap_b = cap
             if self.group is not None:
                 self.group.ensure(cap, dev)
-            if self._pair_loss and dev.type == "cuda":
-                self.pair_ws = K.group_pair_workspace(cap, dev)
-            if self._lambda_loss and dev.type == "cuda":
-                self.lambda_ws = K.group_lambda_workspace(cap, dev)
+                self.loss_ws = K.group_score_workspace(self.loss_type, cap, dev)
         if nnz > self.cap_n:
             cap = max(nnz, int(self.cap_n * 1.25), 1)
             self.dd = K.DedupWorkspace(cap, dev, self.CH)
@@ -126,9 +122,8 @@ class _Workspace:
 
 class _GroupBufs:
     """Buffers of one batch's group plan (rank losses): the examples' group keys and the workspace both halves of
-    ``K.group_softmax_loss`` use (``K.group_pairwise_loss`` and ``K.group_lambda_loss`` read the plan there; their
-    own intermediates live in the step workspace's ``pair_ws`` / ``lambda_ws``).  Allocated by models with a rank
-    loss only."""
+    ``K.group_softmax_loss`` use (the other group losses read the plan there; their own intermediates live in the
+    step workspace's ``loss_ws``).  Allocated by models with a rank loss only."""
 
     def __init__(self):
         self.keys: torch.Tensor | None = None
@@ -302,8 +297,6 @@ class FactorizationMachine:
             raise ValueError("mode=local needs world_size == 1")
         self.mode = mode
         self.rank_loss = cfg.loss_type in K.GROUP_LOSSES
-        self.pair_loss = cfg.loss_type == K.RANK_PAIR_LOSS
-        self.lambda_loss = cfg.loss_type == K.RANK_LAMBDA_LOSS
         if self.rank_loss and (mode != "local" or self.world > 1):
             raise ValueError(f"loss_type = {cfg.loss_type} needs mode = local and world_size == 1 (groups are formed "
                              f"within one rank's batch), got mode = {mode}, world_size = {self.world}")
@@ -329,7 +322,7 @@ class FactorizationMachine:
         self.K, self.Kp = self.table.K, self.table.Kp
         self.rps = rows_per_shard(cfg.vocabulary_size, self.world) if sharded else cfg.vocabulary_size
         self.ws = _Workspace(self.device, self.Kp, cfg.dedup_chunk, K.r1_dtype(cfg.dtype),
-                             group_loss=self.rank_loss, pair_loss=self.pair_loss, lambda_loss=self.lambda_loss)
+                             loss_type=cfg.loss_type)
         self.global_step = 0
         self._side = None
         # lookahead dedup plans (eager local path): the current step's plan and up to two pending
@@ -599,17 +592,9 @@ class FactorizationMachine:
                               bias=self.gbias, **extra)
             if gplan_ready is not None:
                 gplan_ready()
-            if self.lambda_loss:
-                dpred, loss_sum = K.group_lambda_loss(gplan, fo.pred[: sb.B], sb.labels, cfg.rank_lambda_cutoff,
-                                                      self.grad_scale(total_B), dpred=ws.dpred[e0:e1],
-                                                      ws=ws.lambda_ws)
-            elif self.pair_loss:
-                dpred, loss_sum = K.group_pairwise_loss(gplan, fo.pred[: sb.B], sb.labels, sb.weights,
-                                                        self.grad_scale(total_B), dpred=ws.dpred[e0:e1],
-                                                        ws=ws.pair_ws)
-            else:
-                dpred, loss_sum = K.group_softmax_loss(gplan, fo.pred[: sb.B], sb.labels, sb.weights,
-                                                       self.grad_scale(total_B), dpred=ws.dpred[e0:e1])
+            dpred, loss_sum = K.group_loss(cfg.loss_type, gplan, fo.pred[: sb.B], sb.labels, sb.weights,
+                                           self.grad_scale(total_B), cutoff=cfg.rank_lambda_cutoff,
+                                           dpred=ws.dpred[e0:e1], ws=ws.loss_ws)
             return K.FwdOut(fo.pred, fo.r1, dpred, loss_sum, None, None)
         return K.fm_forward(sb.offsets, rows, sb.vals, src_v, src_w, self.Kp, labels=sb.labels, weights=sb.weights,
                             loss=cfg.loss_type, grad_scale=self.grad_scale(total_B), want_r1=True,
@@ -792,12 +777,8 @@ class FactorizationMachine:
                               max_feats=b.max_feats)
             keys = K.group_keys(b.offsets, rows, self.cfg.rank_group_feature, self.table.rows)
             plan = K.group_plan(keys, bits_for(self.table.rows + 1))
-            if loss == K.RANK_LAMBDA_LOSS:
-                fo.dpred, fo.loss_sum = K.group_lambda_loss(plan, fo.pred, b.labels, self.cfg.rank_lambda_cutoff,
-                                                            1.0)
-                return fo
-            op = K.group_pairwise_loss if loss == K.RANK_PAIR_LOSS else K.group_softmax_loss
-            fo.dpred, fo.loss_sum = op(plan, fo.pred, b.labels, b.weights, 1.0)
+            fo.dpred, fo.loss_sum = K.group_loss(loss, plan, fo.pred, b.labels, b.weights, 1.0,
+                                                 cutoff=self.cfg.rank_lambda_cutoff)
             return fo
         return K.fm_forward(b.offsets, rows, b.vals, self.table.v, self.table.w, self.Kp, labels=b.labels,
                             weights=b.weights, loss=loss, grad_scale=1.0, want_r1=want_r1, want_reg=want_reg,

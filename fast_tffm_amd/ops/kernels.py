@@ -1669,6 +1669,41 @@ def group_plan(keys: torch.Tensor, key_bits: int, *, ws: torch.Tensor | None = N
     return GroupPlan(n, key_bits, ws, sidx, first, end, err)
 
 
+def _group_score_half(name: str, op: str, ws_bytes: str, own_ws: bool, plan: GroupPlan, scores: torch.Tensor,
+                      labels: torch.Tensor, weights: torch.Tensor | None, op_args: dict, grad_scale: float,
+                      dpred: torch.Tensor | None, ws: torch.Tensor | None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The score half of a group loss, ``name`` in its messages: the checks, ``dpred``, the empty plan, then the
+    native ``op`` -- the CPU loop over the plan, or the GPU op on the current stream -- with ``op_args`` (``weights``
+    or ``cutoff``) beside the common arguments.  The GPU workspace has ``ws_bytes(n)`` bytes; when ``ws`` is None it
+    is allocated (``own_ws``) or the plan's."""
+    dev = scores.device
+    n = plan.n
+    _check(scores.numel() == n, f"{name}: the plan has {n} examples, scores {scores.numel()}")
+    _chk_vec(scores, torch.float32, n, "scores", dev)
+    _chk_vec(labels, torch.float32, n, "labels", dev)
+    _chk_vec(weights, torch.float32, n, "weights", dev)
+    _check(plan.sidx.device == dev, f"{name}: the plan lives on another device")
+    if dpred is None:
+        dpred = torch.empty(n, dtype=torch.float32, device=dev)
+    _chk_vec(dpred, torch.float32, n, "dpred", dev)
+    if n == 0:
+        return dpred[:0], torch.zeros((), dtype=torch.float32, device=dev)
+    common = dict(n=n, scores=_p(scores), labels=_p(labels), grad_scale=float(grad_scale), dpred=_p(dpred), **op_args)
+    if not _is_gpu(scores):
+        _check(ws is None, f"{name}: the workspace is a GPU argument")
+        ls = getattr(native.cpu(), op)(sidx=_p(plan.sidx), first=_p(plan.first), end=_p(plan.end), **common)
+        return dpred[:n], torch.tensor(ls, dtype=torch.float32)
+    h = native.hip()
+    need = int(getattr(h, ws_bytes)(n))
+    if ws is None:
+        ws = torch.empty(need, dtype=torch.uint8, device=dev) if own_ws else plan.ws
+    _chk_vec(ws, torch.uint8, need, "ws", dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    getattr(h, op)(plan=_p(plan.ws), plan_bytes=plan.ws.numel(), loss=_p(loss), ws=_p(ws), ws_bytes=ws.numel(),
+                   stream=_stream(scores), **common)
+    return dpred[:n], loss
+
+
 def group_softmax_loss(plan: GroupPlan, scores: torch.Tensor, labels: torch.Tensor, weights: torch.Tensor | None,
                        grad_scale: float = 1.0, *, dpred: torch.Tensor | None = None,
                        ws: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
@@ -1682,33 +1717,8 @@ def group_softmax_loss(plan: GroupPlan, scores: torch.Tensor, labels: torch.Tens
     group.  Everything is fp64 (exp and log too) summed in a fixed order and rounded to fp32 once: bitwise the
     same run to run.  GPU: hip/group_loss.hip on the current stream, no host read (capturable); ``ws``: the
     workspace of the intermediates, the plan's own by default.  CPU: a loop over the plan."""
-    dev = scores.device
-    n = plan.n
-    _check(scores.numel() == n, f"group_softmax_loss: the plan has {n} examples, scores {scores.numel()}")
-    _chk_vec(scores, torch.float32, n, "scores", dev)
-    _chk_vec(labels, torch.float32, n, "labels", dev)
-    _chk_vec(weights, torch.float32, n, "weights", dev)
-    _check(plan.sidx.device == dev, "group_softmax_loss: the plan lives on another device")
-    if dpred is None:
-        dpred = torch.empty(n, dtype=torch.float32, device=dev)
-    _chk_vec(dpred, torch.float32, n, "dpred", dev)
-    if n == 0:
-        return dpred[:0], torch.zeros((), dtype=torch.float32, device=dev)
-    if not _is_gpu(scores):
-        _check(ws is None, "group_softmax_loss: the workspace is a GPU argument")
-        ls = native.cpu().group_softmax(n=n, sidx=_p(plan.sidx), first=_p(plan.first), end=_p(plan.end),
-                                        scores=_p(scores), labels=_p(labels), weights=_p(weights),
-                                        grad_scale=float(grad_scale), dpred=_p(dpred))
-        return dpred[:n], torch.tensor(ls, dtype=torch.float32)
-    h = native.hip()
-    if ws is None:
-        ws = plan.ws
-    _chk_vec(ws, torch.uint8, int(h.group_loss_workspace_bytes(n)), "ws", dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    h.group_softmax(plan=_p(plan.ws), plan_bytes=plan.ws.numel(), n=n, scores=_p(scores), labels=_p(labels),
-                    weights=_p(weights), grad_scale=float(grad_scale), dpred=_p(dpred), loss=_p(loss), ws=_p(ws),
-                    ws_bytes=ws.numel(), stream=_stream(scores))
-    return dpred[:n], loss
+    return _group_score_half("group_softmax_loss", "group_softmax", "group_loss_workspace_bytes", False, plan, scores,
+                             labels, weights, {"weights": _p(weights)}, grad_scale, dpred, ws)
 
 
 # ---------------------------------------------------------------------------
@@ -1746,34 +1756,8 @@ def group_pairwise_loss(plan: GroupPlan, scores: torch.Tensor, labels: torch.Ten
     fp32 once: bitwise the same run to run.  The cost is ``sum_g P_g N_g`` pairs.  GPU: hip/group_pair.hip on the
     current stream, no host read (capturable); the plan is only read; ``ws``: ``group_pair_workspace`` (allocated
     when None).  CPU: a loop over the plan."""
-    dev = scores.device
-    n = plan.n
-    _check(scores.numel() == n, f"group_pairwise_loss: the plan has {n} examples, scores {scores.numel()}")
-    _chk_vec(scores, torch.float32, n, "scores", dev)
-    _chk_vec(labels, torch.float32, n, "labels", dev)
-    _chk_vec(weights, torch.float32, n, "weights", dev)
-    _check(plan.sidx.device == dev, "group_pairwise_loss: the plan lives on another device")
-    if dpred is None:
-        dpred = torch.empty(n, dtype=torch.float32, device=dev)
-    _chk_vec(dpred, torch.float32, n, "dpred", dev)
-    if n == 0:
-        return dpred[:0], torch.zeros((), dtype=torch.float32, device=dev)
-    if not _is_gpu(scores):
-        _check(ws is None, "group_pairwise_loss: the workspace is a GPU argument")
-        ls = native.cpu().group_pairwise(n=n, sidx=_p(plan.sidx), first=_p(plan.first), end=_p(plan.end),
-                                         scores=_p(scores), labels=_p(labels), weights=_p(weights),
-                                         grad_scale=float(grad_scale), dpred=_p(dpred))
-        return dpred[:n], torch.tensor(ls, dtype=torch.float32)
-    h = native.hip()
-    need = int(h.group_pair_workspace_bytes(n))
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    _chk_vec(ws, torch.uint8, need, "ws", dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    h.group_pairwise(plan=_p(plan.ws), plan_bytes=plan.ws.numel(), n=n, scores=_p(scores), labels=_p(labels),
-                     weights=_p(weights), grad_scale=float(grad_scale), dpred=_p(dpred), loss=_p(loss), ws=_p(ws),
-                     ws_bytes=ws.numel(), stream=_stream(scores))
-    return dpred[:n], loss
+    return _group_score_half("group_pairwise_loss", "group_pairwise", "group_pair_workspace_bytes", True, plan, scores,
+                             labels, weights, {"weights": _p(weights)}, grad_scale, dpred, ws)
 
 
 # ---------------------------------------------------------------------------
@@ -1814,36 +1798,36 @@ def group_lambda_loss(plan: GroupPlan, scores: torch.Tensor, labels: torch.Tenso
     stable sorts of n and about ``sum_g 2 n_g min(cutoff, n_g)`` pairs (``n_g^2`` when cutoff is 0).  GPU:
     hip/group_lambda.hip on the current stream, no host read (capturable); the plan is only read; ``ws``:
     ``group_lambda_workspace`` (allocated when None).  CPU: a loop over the plan."""
-    dev = scores.device
-    n = plan.n
     cutoff = int(cutoff)
     _check(0 <= cutoff <= RANK_LAMBDA_MAX_CUTOFF,
            f"group_lambda_loss: the cutoff must be in [0, {RANK_LAMBDA_MAX_CUTOFF}], got {cutoff}")
-    _check(scores.numel() == n, f"group_lambda_loss: the plan has {n} examples, scores {scores.numel()}")
-    _chk_vec(scores, torch.float32, n, "scores", dev)
-    _chk_vec(labels, torch.float32, n, "labels", dev)
-    _check(plan.sidx.device == dev, "group_lambda_loss: the plan lives on another device")
-    if dpred is None:
-        dpred = torch.empty(n, dtype=torch.float32, device=dev)
-    _chk_vec(dpred, torch.float32, n, "dpred", dev)
-    if n == 0:
-        return dpred[:0], torch.zeros((), dtype=torch.float32, device=dev)
-    if not _is_gpu(scores):
-        _check(ws is None, "group_lambda_loss: the workspace is a GPU argument")
-        ls = native.cpu().group_lambda(n=n, sidx=_p(plan.sidx), first=_p(plan.first), end=_p(plan.end),
-                                       scores=_p(scores), labels=_p(labels), cutoff=cutoff,
-                                       grad_scale=float(grad_scale), dpred=_p(dpred))
-        return dpred[:n], torch.tensor(ls, dtype=torch.float32)
-    h = native.hip()
-    need = int(h.group_lambda_workspace_bytes(n))
-    if ws is None:
-        ws = torch.empty(need, dtype=torch.uint8, device=dev)
-    _chk_vec(ws, torch.uint8, need, "ws", dev)
-    loss = torch.empty((), dtype=torch.float32, device=dev)
-    h.group_lambda(plan=_p(plan.ws), plan_bytes=plan.ws.numel(), n=n, scores=_p(scores), labels=_p(labels),
-                   cutoff=cutoff, grad_scale=float(grad_scale), dpred=_p(dpred), loss=_p(loss), ws=_p(ws),
-                   ws_bytes=ws.numel(), stream=_stream(scores))
-    return dpred[:n], loss
+    return _group_score_half("group_lambda_loss", "group_lambda", "group_lambda_workspace_bytes", True, plan, scores,
+                             labels, None, {"cutoff": cutoff}, grad_scale, dpred, ws)
+
+
+# ---------------------------------------------------------------------------
+# the group losses by loss_type
+# ---------------------------------------------------------------------------
+def group_loss(loss_type: str, plan: GroupPlan, scores: torch.Tensor, labels: torch.Tensor,
+               weights: torch.Tensor | None, grad_scale: float = 1.0, *, cutoff: int = 0,
+               dpred: torch.Tensor | None = None, ws: torch.Tensor | None = None) -> tuple[torch.Tensor, torch.Tensor]:
+    """The score half of the group loss ``loss_type`` (one of ``GROUP_LOSSES``): ``group_softmax_loss``,
+    ``group_pairwise_loss`` or ``group_lambda_loss`` -- which takes ``cutoff`` and ignores ``weights``."""
+    _check(loss_type in GROUP_LOSSES, f"group_loss: loss_type must be one of {GROUP_LOSSES}, got {loss_type!r}")
+    if loss_type == RANK_LAMBDA_LOSS:
+        return group_lambda_loss(plan, scores, labels, cutoff, grad_scale, dpred=dpred, ws=ws)
+    op = group_pairwise_loss if loss_type == RANK_PAIR_LOSS else group_softmax_loss
+    return op(plan, scores, labels, weights, grad_scale, dpred=dpred, ws=ws)
+
+
+def group_score_workspace(loss_type: str, n: int, device: torch.device) -> torch.Tensor | None:
+    """The score half's own device scratch for up to ``n`` examples; None for ``rank_softmax``, whose score half
+    works in the plan's workspace, and on the CPU."""
+    _check(loss_type in GROUP_LOSSES, f"group_score_workspace: loss_type must be one of {GROUP_LOSSES}, "
+                                      f"got {loss_type!r}")
+    if loss_type == RANK_LOSS or torch.device(device).type != "cuda":
+        return None
+    return (group_lambda_workspace if loss_type == RANK_LAMBDA_LOSS else group_pair_workspace)(n, device)
 
 
 # ---------------------------------------------------------------------------

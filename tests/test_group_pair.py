@@ -213,7 +213,7 @@ def test_model_refuses_other_modes_and_ranks():
                                  "cpu", dist=one)
     m = FactorizationMachine(FMConfig(vocabulary_size=100, factor_num=4, loss_type="rank_pairwise",
                                       rank_group_feature=1), "cpu")
-    assert m.rank_loss and m.pair_loss and m.ws.pair_ws is None
+    assert m.rank_loss and m.ws.loss_type == K.RANK_PAIR_LOSS and m.ws.loss_ws is None
     m.close()
 
 

@@ -2,7 +2,7 @@
 tests/test_rank_pair_step_gpu.py: ``forward(b, loss="rank_lambda")`` is the oracle's loss of the model's own scores
 under the step's key rule; every executor of the local step -- plain, both lookahead depths, ``capture_graph`` replay,
 the lookahead graph ring -- leaves the table and the losses bitwise the same after 6 steps; only a lambda model
-allocates the lambda workspace."""
+allocates the lambda workspace, and it never touches another group loss's op or workspace."""
 
 import pytest
 import torch
@@ -53,17 +53,18 @@ def test_executors_agree_bitwise(plain, executor, monkeypatch):
 
 
 def test_only_a_lambda_model_allocates_the_lambda_workspace(monkeypatch):
-    b = S._batches()[0]
-    m = _model()
-    m.train_step(b)
-    assert m.ws.lambda_ws.numel() >= K.group_lambda_workspace(S.B, m.device).numel() and m.ws.pair_ws is None
-    m.close()
-
     def boom(*a, **k):
-        raise AssertionError("a model without the lambda loss called it")
+        raise AssertionError("a model called another loss's op or workspace")
 
+    b = S._batches()[0]
+    need = K.group_lambda_workspace(S.B, b.labels.device).numel()
+    for name in ("group_pairwise_loss", "group_pair_workspace", "group_softmax_loss"):
+        monkeypatch.setattr(K, name, boom)
+    m = _model()
+    assert m.train_step(b).mean_loss() > 0 and m.ws.loss_ws.numel() >= need
+    m.close()
     for name in ("group_lambda_loss", "group_lambda_workspace"):
         monkeypatch.setattr(K, name, boom)
     m = _model("logistic")
-    assert m.train_step(b).mean_loss() > 0 and m.ws.lambda_ws is None
+    assert m.train_step(b).mean_loss() > 0 and m.ws.loss_ws is None
     m.close()

@@ -121,7 +121,9 @@ def test_logistic_model_never_touches_the_group_loss(monkeypatch):
     def boom(*a, **k):
         raise AssertionError("a pointwise model called the listwise loss")
 
-    for name in ("group_keys", "group_plan", "group_softmax_loss", "group_loss_workspace"):
+    for name in ("group_keys", "group_plan", "group_softmax_loss", "group_loss_workspace", "group_loss",
+                 "group_score_workspace", "group_pairwise_loss", "group_pair_workspace", "group_lambda_loss",
+                 "group_lambda_workspace"):
         monkeypatch.setattr(K, name, boom)
     batches = _batches()
     ref = None
@@ -134,7 +136,7 @@ def test_logistic_model_never_touches_the_group_loss(monkeypatch):
             nb = seq[i + 1] if executor == "lookahead" and i + 1 < len(seq) else None
             m.train_step(bt, nb)
         torch.cuda.synchronize()
-        assert m.ws.group is None
+        assert m.ws.group is None and m.ws.loss_ws is None
         assert all(s.group is None and s.gplan is None for s in m._lslots)
         st = _state(m)
         m.close()

@@ -1,8 +1,8 @@
 """The training step with ``loss_type = rank_pairwise`` on the GPU: every executor of the local step -- plain eager
 steps, the depth-1 and depth-2 lookahead, ``capture_graph`` replay and the lookahead graph ring -- leaves the table
 and the losses bitwise the same after 6 steps over 3 cycling batches; one step agrees with the CPU executor's; and a
-``rank_softmax`` and a ``logistic`` model in the same process never touch the pairwise loss (no pair workspace,
-none of its ops called)."""
+``rank_softmax`` and a ``logistic`` model in the same process never touch the pairwise loss (no score-half workspace,
+none of its ops called, nor the LambdaRank loss's)."""
 
 import numpy as np
 import pytest
@@ -75,7 +75,7 @@ def _run(executor, monkeypatch, loss="rank_pairwise"):
     torch.cuda.synchronize()
     K.check_device_errors()
     st = _state(m)
-    pair_ws = m.ws.pair_ws
+    pair_ws = m.ws.loss_ws
     m.close()
     return st, losses, pair_ws
 
@@ -124,11 +124,11 @@ def test_one_step_matches_cpu_executor():
 
 def test_other_models_never_touch_the_pairwise_loss(monkeypatch):
     """A ``rank_softmax`` and a ``logistic`` model train as before -- every executor bitwise equal to the plain one
-    -- with the pairwise op and its workspace made to raise."""
+    -- with the pairwise and the LambdaRank op and their workspaces made to raise."""
     def boom(*a, **k):
         raise AssertionError("a model without the pairwise loss called it")
 
-    for name in ("group_pairwise_loss", "group_pair_workspace"):
+    for name in ("group_pairwise_loss", "group_pair_workspace", "group_lambda_loss", "group_lambda_workspace"):
         monkeypatch.setattr(K, name, boom)
     for loss in ("rank_softmax", "logistic"):
         ref = None
