@@ -61,6 +61,9 @@ Extensions (new keys, all optional):
                 recommend_seen_files = <files> (parallel to predict_files: line i holds the whitespace-separated
                                 0-based candidate lines context i has already seen, in any order, an empty line for
                                 none; ``recommend`` then leaves them out of <file>_recommend and of the places),
+                recommend_shortlist_files = <files> (parallel to predict_files, in the line format of
+                                recommend_seen_files: line i holds the only candidate lines context i is ranked and
+                                placed among -- its target always competes; not together with recommend_seen_files),
                 threshold_metrics = true|false (``evaluate`` then also reports the average precision, KS and
                                 the best F1 and writes <file>_thresholds; default false),
                 precision_targets = <p>[,<p>...] / recall_targets = <r>[,<r>...] (0 to 4 values in (0, 1] each:
@@ -174,6 +177,7 @@ class FMRunConfig:
     rank_cutoffs: list[int] = field(default_factory=list)  # NDCG@K / recall@K / precision@K cutoffs (evaluate)
     recommend_target_files: list[str] = field(default_factory=list)  # one held-out candidate per predict line
     recommend_seen_files: list[str] = field(default_factory=list)    # the already-seen candidates of each predict line
+    recommend_shortlist_files: list[str] = field(default_factory=list)  # the only candidates of each predict line
     validation_ap: bool = False          # report the average precision of the validation scores
     ap_tolerance: float | None = None    # stop when the validation average precision is >= this
     threshold_metrics: bool = False      # evaluate: average precision, KS, best F1 and <file>_thresholds
@@ -415,6 +419,14 @@ def load_config(config_file: str, *, echo: bool = True, printer=print) -> FMRunC
         c.recommend_seen_files = _expand(rsf, base_dir)
         if len(c.predict_files) != len(c.recommend_seen_files):
             raise ConfigError("The numbers of predict files and recommend seen files do not match.")
+    rlf = read_list(PREDICT, "recommend_shortlist_files", required=False)
+    if rlf is not None:
+        c.recommend_shortlist_files = _expand(rlf, base_dir)
+        if len(c.predict_files) != len(c.recommend_shortlist_files):
+            raise ConfigError("The numbers of predict files and recommend shortlist files do not match.")
+        if c.recommend_seen_files:
+            raise ConfigError("recommend_shortlist_files and recommend_seen_files cannot be set together "
+                              "(take the seen candidates out of the shortlists).")
     rc =read_list(PREDICT, "rank_cutoffs", required=False)
     if rc is not None:
         c.rank_cutoffs = _cutoffs("rank_cutoffs", rc, 4)

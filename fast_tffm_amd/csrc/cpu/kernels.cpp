@@ -935,7 +935,7 @@ void calib_apply(long long n, const float* scores, const float* x, const float* 
 
 void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q_stride, const float* C,
           long long c_stride, const float* qb, const float* cb, int* idx, float* score, int threads,
-          const int* seen_off, const int* seen_idx) {
+          const int* seen_off, const int* seen_idx, const int* short_off, const int* short_idx) {
   set_threads(threads);
   std::vector<int> cols;  // pi(Kp)
   topk::for_each_col(Kp, [&](int c) { cols.push_back(c); });
@@ -950,12 +950,7 @@ void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q
       const float* qr = Q + q * q_stride;
       for (size_t i = 0; i < cols.size(); ++i) qv[i] = qr[cols[i]];
       heap.clear();
-      // the query's seen list (ascending, as c is): sp walks it
-      int sp = seen_off ? seen_off[q] : 0;
-      const int se = seen_off ? seen_off[q + 1] : 0;
-      for (long long c = 0; c < nc; ++c) {
-        while (sp < se && seen_idx[sp] < c) ++sp;
-        if (sp < se && seen_idx[sp] == c) continue;
+      const auto rank = [&](long long c) {
         const float* cr = C + c * c_stride;
         float dot = 0.f;
         for (size_t i = 0; i < cols.size(); ++i) dot = std::fmaf(qv[i], cr[cols[i]], dot);
@@ -974,6 +969,19 @@ void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q
           heap.back() = key;
           std::push_heap(heap.begin(), heap.end(), gt);
         }
+      };
+      if (short_off) {  // the query's shortlist alone (an index outside [0, nc) is skipped, as on the GPU)
+        for (int p = short_off[q]; p < short_off[q + 1]; ++p)
+          if (short_idx[p] >= 0 && short_idx[p] < nc) rank(short_idx[p]);
+      } else {
+        // the query's seen list (ascending, as c is): sp walks it
+        int sp = seen_off ? seen_off[q] : 0;
+        const int se = seen_off ? seen_off[q + 1] : 0;
+        for (long long c = 0; c < nc; ++c) {
+          while (sp < se && seen_idx[sp] < c) ++sp;
+          if (sp < se && seen_idx[sp] == c) continue;
+          rank(c);
+        }
       }
       std::sort(heap.begin(), heap.end(), gt);
       for (int t = 0; t < k; ++t) {
@@ -988,7 +996,7 @@ void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q
 
 void place(long long nq, long long nc, int Kp, const float* Q, long long q_stride, const float* C,
            long long c_stride, const float* qb, const float* cb, const int* target, int* counts, int threads,
-           const int* seen_off, const int* seen_idx) {
+           const int* seen_off, const int* seen_idx, const int* short_off, const int* short_idx) {
   set_threads(threads);
   std::vector<int> cols;  // pi(Kp)
   topk::for_each_col(Kp, [&](int c) { cols.push_back(c); });
@@ -1011,9 +1019,19 @@ void place(long long nq, long long nc, int Kp, const float* Q, long long q_strid
           return sum + 0.f;
         };
         const float st = score(t);
+        if (short_off) {  // the query's shortlist and the target, which counts once whether or not it is listed
+          eq = 1;
+          for (int p = short_off[q]; p < short_off[q + 1]; ++p) {
+            const int c = short_idx[p];
+            if (c < 0 || c >= nc || c == t) continue;
+            const float s = score(c);
+            gt += s > st;
+            eq += s == st;
+          }
+        }
         int sp = seen_off ? seen_off[q] : 0;
         const int se = seen_off ? seen_off[q + 1] : 0;
-        for (long long c = 0; c < nc; ++c) {
+        for (long long c = 0; c < (short_off ? 0 : nc); ++c) {
           while (sp < se && seen_idx[sp] < c) ++sp;
           if (sp < se && seen_idx[sp] == c && c != t) continue;  // (the target competes even when it is listed)
           const float s = score(c);

@@ -33,18 +33,22 @@ void explain(int B, const int* offsets, const int* rows, const float* vals, cons
 // The k best candidates of every query from FM profiles (hip/fm_topk.hip: same definition, bit for bit):
 // s = ((qb[q] + cb[c]) + fmaf chain over pi(Kp)) + 0.f, greater s first, equal s by ascending candidate;
 // idx = -1 / score = -inf where nc < k (../topk_order.h).  seen_off [nq + 1] / seen_idx (or null: none): CSR lists
-// of the candidates each query leaves out, ascending within a query (hip/fm_seen.hip).
+// of the candidates each query leaves out, ascending within a query (hip/fm_seen.hip).  short_off / short_idx (or
+// null): lists of the same layout of the only candidates each query ranks (hip/fm_shortlist.hip; not with seen).
 void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q_stride, const float* C,
           long long c_stride, const float* qb, const float* cb, int* idx, float* score, int threads,
-          const int* seen_off = nullptr, const int* seen_idx = nullptr);
+          const int* seen_off = nullptr, const int* seen_idx = nullptr, const int* short_off = nullptr,
+          const int* short_idx = nullptr);
 
 // The place of a held-out candidate among all candidates (hip/fm_place.hip: same definition, word for word):
 // with topk's score s, counts[q] = (#{c : s(q, c) > s(q, t)}, #{c : s(q, c) == s(q, t)}), t = target[q]; a target
 // outside [0, nc) leaves (0, 0): unranked.  With seen lists (as topk's) a query's listed candidates other than its
-// target are not counted.
+// target are not counted.  With shortlists (as topk's) the competitors are a query's list and its target: the
+// listed candidates other than the target are counted, and equal starts at 1 for the target.
 void place(long long nq, long long nc, int Kp, const float* Q, long long q_stride, const float* C,
            long long c_stride, const float* qb, const float* cb, const int* target, int* counts, int threads,
-           const int* seen_off = nullptr, const int* seen_idx = nullptr);
+           const int* seen_off = nullptr, const int* seen_idx = nullptr, const int* short_off = nullptr,
+           const int* short_idx = nullptr);
 
 // The record of n (greater, equal) rows at the nk cutoffs k (../place_order.h; equal <= 0: unranked): rec[2 + 3 nk]
 // 64-bit words = ranked contexts, sum of a + b (int64), then hit, ndcg, mrr sums per cutoff (fp64), added per tile

@@ -371,15 +371,19 @@ PYBIND11_MODULE(_fm_cpu, m) {
   m.def(
       "topk",
       [](long long nq, long long nc, int Kp, int k, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb,
-         u64 cb, u64 idx, u64 score, int threads, u64 seen_off, u64 seen_idx) {
+         u64 cb, u64 idx, u64 score, int threads, u64 seen_off, u64 seen_idx, u64 shortlist_off, u64 shortlist_idx) {
         py::gil_scoped_release nogil;
         fm::cpu::topk(nq, nc, Kp, k, P<const float>(q), q_stride, P<const float>(c), c_stride, P<const float>(qb),
                       P<const float>(cb), P<int>(idx), P<float>(score), threads, P<const int>(seen_off),
-                      P<const int>(seen_idx));
+                      P<const int>(seen_idx), P<const int>(shortlist_off), P<const int>(shortlist_idx));
       },
       py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("k"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
       py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("idx"), py::arg("score"), py::arg("threads"),
-      py::arg("seen_off") = 0, py::arg("seen_idx") = 0);
+      py::arg("seen_off") = 0, py::arg("seen_idx") = 0, py::arg("shortlist_off") = 0, py::arg("shortlist_idx") = 0);
+  m.def(
+      "shortlist_plan",
+      [](long long nq, long long nnz, long long nc) { return fm::topk::shortlist_plan(nq, nnz, nc); }, py::arg("nq"),
+      py::arg("nnz"), py::arg("nc"));
 
   m.def(
       "place_plan",
@@ -391,15 +395,15 @@ PYBIND11_MODULE(_fm_cpu, m) {
   m.def(
       "place",
       [](long long nq, long long nc, int Kp, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb, u64 cb,
-         u64 target, u64 counts, int threads, u64 seen_off, u64 seen_idx) {
+         u64 target, u64 counts, int threads, u64 seen_off, u64 seen_idx, u64 shortlist_off, u64 shortlist_idx) {
         py::gil_scoped_release nogil;
         fm::cpu::place(nq, nc, Kp, P<const float>(q), q_stride, P<const float>(c), c_stride, P<const float>(qb),
                        P<const float>(cb), P<const int>(target), P<int>(counts), threads, P<const int>(seen_off),
-                       P<const int>(seen_idx));
+                       P<const int>(seen_idx), P<const int>(shortlist_off), P<const int>(shortlist_idx));
       },
       py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
       py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("target"), py::arg("counts"), py::arg("threads"),
-      py::arg("seen_off") = 0, py::arg("seen_idx") = 0);
+      py::arg("seen_off") = 0, py::arg("seen_idx") = 0, py::arg("shortlist_off") = 0, py::arg("shortlist_idx") = 0);
   m.def(
       "place_metrics",
       [](long long n, u64 counts, const std::vector<int>& cutoffs, u64 rec) {

@@ -36,6 +36,7 @@ using u64 = std::uintptr_t;
 #include "rank_metrics.hip"
 #include "fm_place.hip"
 #include "fm_seen.hip"
+#include "fm_shortlist.hip"
 #include "group_loss.hip"
 #include "group_walk.hip"
 #include "group_pair.hip"
@@ -185,13 +186,20 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
   m.def(
       "topk",  // the k best candidates of every query from profiles (fm_topk.hip): idx [nq, k], score [nq, k]
       [](long long nq, long long nc, int Kp, int k, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb,
-         u64 cb, u64 ws, size_t ws_bytes, u64 idx, u64 score, u64 stream, u64 seen_off, u64 seen_idx, int seen_nnz) {
-        if ((long long)ws_bytes < fm::topk_workspace_bytes(nq, nc, k)) throw std::runtime_error("topk: workspace too small");
+         u64 cb, u64 ws, size_t ws_bytes, u64 idx, u64 score, u64 stream, u64 seen_off, u64 seen_idx, int seen_nnz,
+         u64 shortlist_off, u64 shortlist_idx, int shortlist_nnz) {
+        if (!shortlist_off && (long long)ws_bytes < fm::topk_workspace_bytes(nq, nc, k))
+          throw std::runtime_error("topk: workspace too small");
         fm::TopkArgs a{};
         a.nq = nq; a.nc = nc; a.Kp = Kp; a.k = k; a.Q = P<const float>(q); a.q_stride = q_stride;
         a.C = P<const float>(c); a.c_stride = c_stride; a.qb = P<const float>(qb); a.cb = P<const float>(cb);
         a.ws = P<unsigned long long>(ws); a.idx = P<int>(idx); a.score = P<float>(score);
-        if (seen_off) {  // (fm_seen.hip; no list: the plain kernels with the plain arguments)
+        if (shortlist_off) {  // (fm_shortlist.hip: the walk over every query's own list)
+          const fm::SeenArgs sl{P<const int>(shortlist_off), P<const int>(shortlist_idx), shortlist_nnz};
+          const int rc = fm::launch_topk_shortlist(a, sl, ws_bytes, S(stream));
+          if (rc == -2) throw std::runtime_error("topk: workspace too small");
+          check(rc, "fm_topk (shortlist)");
+        } else if (seen_off) {  // (fm_seen.hip; no list: the plain kernels with the plain arguments)
           const fm::SeenArgs sn{P<const int>(seen_off), P<const int>(seen_idx), seen_nnz};
           check(fm::launch_topk_seen(a, sn, S(stream)), "fm_topk (seen)");
         } else {
@@ -200,7 +208,14 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       },
       py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("k"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
       py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("ws"), py::arg("ws_bytes"), py::arg("idx"),
-      py::arg("score"), py::arg("stream"), py::arg("seen_off") = 0, py::arg("seen_idx") = 0, py::arg("seen_nnz") = 0);
+      py::arg("score"), py::arg("stream"), py::arg("seen_off") = 0, py::arg("seen_idx") = 0, py::arg("seen_nnz") = 0,
+      py::arg("shortlist_off") = 0, py::arg("shortlist_idx") = 0, py::arg("shortlist_nnz") = 0);
+  m.def(
+      "shortlist_plan",  // parts of a call with shortlists: runs per query's list (topk_order.h)
+      [](long long nq, long long nnz, long long nc) { return fm::topk::shortlist_plan(nq, nnz, nc); }, py::arg("nq"),
+      py::arg("nnz"), py::arg("nc"));
+  m.def("shortlist_workspace_bytes", &fm::shortlist_workspace_bytes, py::arg("nq"), py::arg("nnz"), py::arg("nc"),
+        py::arg("k"));
 
   m.def(
       "place_plan",  // (slab, parts) of a place call: candidates per slab, partial counts per query (place_order.h)
@@ -215,14 +230,18 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       "place",  // the held-out candidate's place (fm_place.hip): counts [nq, 2] int32 and the record [2 + 3 nk]
       [](long long nq, long long nc, int Kp, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb, u64 cb,
          u64 target, const std::vector<int>& cutoffs, u64 counts, u64 rec, u64 ws, size_t ws_bytes, u64 stream,
-         u64 seen_off, u64 seen_idx, int seen_nnz) {
+         u64 seen_off, u64 seen_idx, int seen_nnz, u64 shortlist_off, u64 shortlist_idx, int shortlist_nnz) {
         fm::PlaceArgs a{};
         a.nq = nq; a.nc = nc; a.Kp = Kp; a.Q = P<const float>(q); a.q_stride = q_stride; a.C = P<const float>(c);
         a.c_stride = c_stride; a.qb = P<const float>(qb); a.cb = P<const float>(cb); a.target = P<const int>(target);
         a.counts = P<int>(counts);
         const fm::SeenArgs sn{P<const int>(seen_off), P<const int>(seen_idx), seen_nnz};
-        const int rc = fm::launch_place(a, cutoffs.data(), (int)cutoffs.size(), P<void>(rec), P<void>(ws), ws_bytes,
-                                        S(stream), seen_off ? &sn : nullptr);
+        const fm::SeenArgs sl{P<const int>(shortlist_off), P<const int>(shortlist_idx), shortlist_nnz};
+        const int rc = shortlist_off  // (fm_shortlist.hip: the walk over every query's own list)
+                           ? fm::launch_place_shortlist(a, sl, cutoffs.data(), (int)cutoffs.size(), P<void>(rec),
+                                                        P<void>(ws), ws_bytes, S(stream))
+                           : fm::launch_place(a, cutoffs.data(), (int)cutoffs.size(), P<void>(rec), P<void>(ws),
+                                              ws_bytes, S(stream), seen_off ? &sn : nullptr);
         if (rc == -2) throw std::runtime_error("place: workspace too small");
         if (rc == -7) throw std::invalid_argument("place: 1 to 4 strictly ascending cutoffs in [1, 4096]");
         check(rc, "fm_place");
@@ -230,7 +249,8 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
       py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("target"), py::arg("cutoffs"), py::arg("counts"),
       py::arg("rec"), py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"), py::arg("seen_off") = 0,
-      py::arg("seen_idx") = 0, py::arg("seen_nnz") = 0);
+      py::arg("seen_idx") = 0, py::arg("seen_nnz") = 0, py::arg("shortlist_off") = 0, py::arg("shortlist_idx") = 0,
+      py::arg("shortlist_nnz") = 0);
   m.def(
       "place_metrics",  // the reduce pass of fm_place.hip alone: the record of n (greater, equal) rows
       [](long long n, u64 counts, const std::vector<int>& cutoffs, u64 rec, u64 ws, size_t ws_bytes, u64 stream) {

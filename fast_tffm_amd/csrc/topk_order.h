@@ -75,5 +75,29 @@ inline Plan plan(long long nq, long long nc, int /*k*/) {
   return Plan{slab, (int)parts};
 }
 
+// ---- the shortlist plan ----------------------------------------------------------------------------
+// With a shortlist per query (hip/fm_shortlist.hip) one wave walks one (query, part) pair: a query's list of len
+// entries is cut into `parts` runs of ceil(len / parts) entries rounded up to a whole number of 64-entry steps, so
+// most parts of a short list are empty.  A pure function of the sizes: enough waves to fill the chip when there
+// are few queries (kTargetWaves / nq, at most kMaxParts), and never more parts than the longest possible list --
+// min(nnz, nc) entries -- has runs of kMinPart entries, so that the selection's warm-up (the first two steps always
+// end in a sort) stays a small share of a part.  100 000 queries of 200 candidates run one part each; one query
+// of 10^6 candidates runs 512.  kMinPart = 256 is kMinSlab's value and reasoning; nothing else was tried.
+constexpr int kMinPart = 256;
+constexpr int kShortStep = 64;   // list entries per step: one key per lane
+inline int shortlist_plan(long long nq, long long nnz, long long nc) {
+  long long want = nq > 0 ? kTargetWaves / nq : 1;
+  if (want > kMaxParts) want = kMaxParts;
+  const long long longest = nnz < nc ? nnz : nc;
+  const long long most = (longest + kMinPart - 1) / kMinPart;
+  if (want > most) want = most;
+  return want < 1 ? 1 : (int)want;
+}
+// Entries per part of a list of len entries (a multiple of kShortStep; 64-bit: len + 64 parts can pass 2^31).
+FM_TOPK_HD inline long long shortlist_run(long long len, int parts) {
+  const long long run = (len + parts - 1) / parts;
+  return (run + kShortStep - 1) / kShortStep * kShortStep;
+}
+
 }  // namespace topk
 }  // namespace fm

@@ -832,28 +832,35 @@ class FactorizationMachine:
         return fo.pred, fo.r1
 
     @torch.no_grad()
-    def recommend(self, contexts: Batch, candidates, k: int, seen=None) -> tuple[torch.Tensor, torch.Tensor]:
+    def recommend(self, contexts: Batch, candidates, k: int, seen=None,
+                  shortlist=None) -> tuple[torch.Tensor, torch.Tensor]:
         """The ``k`` best candidates of every context: ``(idx [B, k] int32, score [B, k] fp32)``, the score of
         the context's and the candidate's features taken together (``K.fm_topk``: greater first, ties by
         ascending candidate, -1 / -inf past the candidate count).  ``candidates``: a ``Batch`` of candidate
         examples, or the ``(pred, S)`` pair ``profile`` returned for one (profile a catalogue once).  ``seen``:
-        the ``(seen_offsets, seen_idx)`` pair of ``K.seen_lists``, per context the candidates to leave out."""
+        the ``(seen_offsets, seen_idx)`` pair of ``K.seen_lists``, per context the candidates to leave out.
+        ``shortlist``: a pair of the same kind, per context the only candidates to rank (not together with
+        ``seen``)."""
         c_pred, c_prof = self.profile(candidates) if isinstance(candidates, Batch) else candidates
         q_pred, q_prof = self.profile(contexts)
         c_base = c_pred - self.gbias if self.gbias is not None else c_pred
-        return K.fm_topk(q_prof, q_pred, c_prof, c_base, k, threads=self.cfg.threads, seen=seen)
+        return K.fm_topk(q_prof, q_pred, c_prof, c_base, k, threads=self.cfg.threads, seen=seen,
+                         shortlist=shortlist)
 
     @torch.no_grad()
-    def place(self, contexts: Batch, candidates, target: torch.Tensor, cutoffs=(10,), seen=None) -> "K.PlaceStats":
+    def place(self, contexts: Batch, candidates, target: torch.Tensor, cutoffs=(10,), seen=None,
+              shortlist=None) -> "K.PlaceStats":
         """The place of every context's held-out candidate among all candidates, by ``recommend``'s score:
         ``target`` int32 ``[B]`` in ``[-1, candidates)`` (-1: no target), ``cutoffs`` 1 to 4 ascending integers in
         [1, 4096]; the lazy record of ``K.fm_place`` (``counts``, ``hit`` / ``ndcg`` / ``mrr`` per cutoff,
         ``mean_place``).  ``candidates``: a ``Batch`` or the ``(pred, S)`` pair of one, as in ``recommend``.
-        ``seen``: as in ``recommend``; a context's listed candidates other than its target do not compete."""
+        ``seen``: as in ``recommend``; a context's listed candidates other than its target do not compete.
+        ``shortlist``: as in ``recommend``; a context's target competes with its listed candidates alone."""
         c_pred, c_prof = self.profile(candidates) if isinstance(candidates, Batch) else candidates
         q_pred, q_prof = self.profile(contexts)
         c_base = c_pred - self.gbias if self.gbias is not None else c_pred
-        return K.fm_place(q_prof, q_pred, c_prof, c_base, target, cutoffs, threads=self.cfg.threads, seen=seen)
+        return K.fm_place(q_prof, q_pred, c_prof, c_base, target, cutoffs, threads=self.cfg.threads, seen=seen,
+                          shortlist=shortlist)
 
     def eval_loss(self, b: Batch) -> float:
         """Weighted mean loss of the configured type (reference valid_op, fm_model.py:317-333)."""

@@ -2032,32 +2032,57 @@ def seen_lists(lists, nc: int, device) -> tuple[torch.Tensor, torch.Tensor]:
     return (torch.tensor(off, dtype=torch.int32, device=device), torch.tensor(idx, dtype=torch.int32, device=device))
 
 
-def _chk_seen(seen, nq: int, nc: int, dev: torch.device, op: str) -> dict:
-    """Validate the ``seen`` pair of ``op`` and return the native call's keyword arguments (none without lists).
-    The values are checked on the CPU and, with FM_DEBUG_CHECKS=1 and outside a capture, on the GPU."""
+def _chk_seen(seen, nq: int, nc: int, dev: torch.device, op: str, arg: str = "seen") -> dict:
+    """Validate the ``seen`` (or, by its name ``arg``, the ``shortlist``) pair of ``op`` and return the native call's
+    keyword arguments (none without lists).  The values are checked on the CPU and, with FM_DEBUG_CHECKS=1 and
+    outside a capture, on the GPU."""
     if seen is None:
         return {}
-    _check(isinstance(seen, (tuple, list)) and len(seen) == 2, f"{op}: seen is the pair (seen_offsets, seen_idx)")
+    _check(isinstance(seen, (tuple, list)) and len(seen) == 2,
+           f"{op}: {arg} is the pair ({arg}_offsets, {arg}_idx)")
     off, idx = seen
-    _chk_vec(off, torch.int32, nq + 1, "seen_offsets", dev)
-    _chk_vec(idx, torch.int32, None, "seen_idx", dev)
-    _check(off.numel() == nq + 1, f"seen_offsets: expected {nq + 1} entries (nq + 1), got {off.numel()}")
+    _chk_vec(off, torch.int32, nq + 1, f"{arg}_offsets", dev)
+    _chk_vec(idx, torch.int32, None, f"{arg}_idx", dev)
+    _check(off.numel() == nq + 1, f"{arg}_offsets: expected {nq + 1} entries (nq + 1), got {off.numel()}")
     nnz = idx.numel()
     if not _is_gpu(off) or (_DEBUG and not torch.cuda.is_current_stream_capturing()):
-        _check(int(off[0]) == 0 and int(off[-1]) == nnz, f"seen_offsets: must run from 0 to {nnz} (seen_idx's length)")
-        _check(bool((off[1:] >= off[:-1]).all()), "seen_offsets: must not decrease")
+        _check(int(off[0]) == 0 and int(off[-1]) == nnz,
+               f"{arg}_offsets: must run from 0 to {nnz} ({arg}_idx's length)")
+        _check(bool((off[1:] >= off[:-1]).all()), f"{arg}_offsets: must not decrease")
         if nnz:
-            _check(bool(idx.min() >= 0) and bool(idx.max() < nc), f"seen_idx: values must be in [0, {nc})")
+            _check(bool(idx.min() >= 0) and bool(idx.max() < nc), f"{arg}_idx: values must be in [0, {nc})")
             up = idx[1:] > idx[:-1]
             starts = off[1:-1].long()
             up[starts[(starts >= 1) & (starts < nnz)] - 1] = True   # (a new context may start lower)
-            _check(bool(up.all()), "seen_idx: a context's indices must be strictly ascending")
-    return dict(seen_off=_p(off), seen_idx=_p(idx), seen_nnz=nnz)
+            _check(bool(up.all()), f"{arg}_idx: a context's indices must be strictly ascending")
+    return {f"{arg}_off": _p(off), f"{arg}_idx": _p(idx), f"{arg}_nnz": nnz}
+
+
+def _chk_lists(seen, shortlist, nq: int, nc: int, dev: torch.device, op: str) -> dict:
+    """The native keyword arguments of ``op``'s ``seen`` or ``shortlist`` (at most one of them)."""
+    if seen is not None and shortlist is not None:
+        raise ValueError(f"{op}: seen and shortlist cannot be given together (subtract one from the other first)")
+    return _chk_seen(seen, nq, nc, dev, op) if shortlist is None else _chk_seen(shortlist, nq, nc, dev, op, "shortlist")
+
+
+def shortlist_plan(nq: int, nnz: int, nc: int) -> int:
+    """The parts every context's list is cut into by an ``fm_topk`` / ``fm_place`` call with ``shortlist`` on the
+    GPU: one wave walks one (context, part) pair (csrc/topk_order.h; a pure function of the sizes, the same from the
+    host module)."""
+    return int(native.cpu().shortlist_plan(int(nq), int(nnz), int(nc)))
+
+
+def shortlist_workspace(nq: int, nnz: int, nc: int, k: int, device: torch.device) -> torch.Tensor:
+    """Device scratch of ``fm_topk(k, shortlist=)`` and of ``fm_place(shortlist=)`` with any cutoffs (GPU), for lists
+    of ``nnz`` entries together: the parts' key lists, or s_t, the ranked flags, the parts' counts and the metric
+    tiles."""
+    return torch.empty(int(native.hip().shortlist_workspace_bytes(int(nq), int(nnz), int(nc), int(k))),
+                       dtype=torch.uint8, device=device)
 
 
 def fm_topk(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_base: torch.Tensor, k: int, *,
             idx: torch.Tensor | None = None, score: torch.Tensor | None = None, ws: torch.Tensor | None = None,
-            threads: int = 0, seen=None) -> tuple[torch.Tensor, torch.Tensor]:
+            threads: int = 0, seen=None, shortlist=None) -> tuple[torch.Tensor, torch.Tensor]:
     """The ``k`` best candidates of every query from FM profiles (hip/fm_topk.hip; the reference only scores).
 
     ``s(q, c) = ((q_base[q] + c_base[c]) + dot) + 0`` with ``dot`` the fp32 fmaf chain of ``q_prof[q]`` and
@@ -2073,14 +2098,20 @@ def fm_topk(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_
     membership search only for a key that beats its row's threshold).  The lists are checked on the CPU and, with
     FM_DEBUG_CHECKS=1, on the GPU; without the check a malformed list gives unspecified membership.  A list that
     covers most of the catalogue is correct but slow: every candidate then pays a search.  ``None`` launches the
-    plain kernels."""
+    plain kernels.
+
+    ``shortlist``: a pair of the same layout and checks, per query the only candidates to rank: row q holds the ``k``
+    best of its list, ``-1`` / ``-inf`` where the list is shorter (hip/fm_shortlist.hip: one wave per (query, part
+    of its list) gathers the listed rows by index; ``ws``: a reusable ``shortlist_workspace``).  Not together with
+    ``seen``.  One huge list among many short ones is correct but slow: it is walked by ``shortlist_plan``'s parts
+    alone."""
     dev = q_prof.device
     _check(isinstance(k, int) and 1 <= k <= TOPK_MAX_K, f"fm_topk: k must be in 1..{TOPK_MAX_K}, got {k}")
     nq, Kp, q_stride = _chk_profiles(q_prof, q_base, "q", dev)
     nc, Kc, c_stride = _chk_profiles(c_prof, c_base, "c", dev)
     _check(Kp == Kc, f"fm_topk: profile widths differ ({Kp} and {Kc})")
     _check(nc < 2**31 and nq < 2**31, "fm_topk: nq and nc must be below 2^31")
-    skw = _chk_seen(seen, nq, nc, dev, "fm_topk")
+    skw = _chk_lists(seen, shortlist, nq, nc, dev, "fm_topk")
     if idx is None:
         idx = torch.empty((nq, k), dtype=torch.int32, device=dev)
     if score is None:
@@ -2095,6 +2126,8 @@ def fm_topk(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_
     if _is_gpu(q_prof):
         h = native.hip()
         need = int(h.topk_workspace_bytes(nq, nc, k))
+        if shortlist is not None:  # (the parts' key lists alone: any shortlist_workspace of these sizes is enough)
+            need = nq * int(h.shortlist_plan(nq, skw["shortlist_nnz"], nc)) * k * 8
         if ws is None:
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
         _chk_vec(ws, torch.uint8, need, "ws", dev)
@@ -2103,6 +2136,7 @@ def fm_topk(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_
     else:
         _check(ws is None, "fm_topk: the workspace is a GPU argument")
         skw.pop("seen_nnz", None)
+        skw.pop("shortlist_nnz", None)
         native.cpu().topk(threads=threads, **kw, **skw)
     return idx, score
 
@@ -2219,7 +2253,7 @@ def place_metrics(counts: torch.Tensor, cutoffs=(10,)) -> PlaceStats:
 
 def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_base: torch.Tensor,
              target: torch.Tensor, cutoffs=(10,), *, counts: torch.Tensor | None = None,
-             ws: torch.Tensor | None = None, threads: int = 0, seen=None) -> PlaceStats:
+             ws: torch.Tensor | None = None, threads: int = 0, seen=None, shortlist=None) -> PlaceStats:
     """The place of every query's held-out candidate among all candidates (hip/fm_place.hip), and the
     leave-one-out metrics it implies.
 
@@ -2239,7 +2273,14 @@ def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c
     ``greater`` and ``equal`` count the ``c`` outside ``E_q \\ {target}`` -- the query's own target always competes,
     so ``equal >= 1`` still holds -- and a query with target ``-1`` stays all zeros.  GPU: one more small launch
     after the count pass (hip/fm_seen.hip) scores the listed candidates with the same fmaf chain and subtracts
-    their counts; the workspace is the same.  ``None`` launches the plain kernels."""
+    their counts; the workspace is the same.  ``None`` launches the plain kernels.
+
+    ``shortlist``: the lists of ``fm_topk(shortlist=)``.  The competitors of a query are its list and its target:
+    ``greater = #{c in L_q, c != t : s(q, c) > s_t}`` and ``equal = 1 + #{c in L_q, c != t : s(q, c) == s_t}`` -- the
+    target always competes, listed or not, an empty list gives ``(0, 1)`` -- and a query with target ``-1`` stays
+    all zeros.  GPU: the target pass, the walk over the lists (hip/fm_shortlist.hip) and the reduce pass; the count
+    pass over the catalogue is not launched (``ws``: a reusable ``shortlist_workspace``).  Not together with
+    ``seen``."""
     ks = _place_cutoffs(cutoffs)
     dev = q_prof.device
     nq, Kp, q_stride = _chk_profiles(q_prof, q_base, "q", dev)
@@ -2250,7 +2291,7 @@ def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c
     _check(target.numel() == nq, "target: one candidate (or -1) per query")
     if nq and (not _is_gpu(target) or (_DEBUG and not torch.cuda.is_current_stream_capturing())):
         _check(bool(target.min() >= -1) and bool(target.max() < nc), f"target: values must be in [-1, {nc})")
-    skw = _chk_seen(seen, nq, nc, dev, "fm_place")
+    skw = _chk_lists(seen, shortlist, nq, nc, dev, "fm_place")
     if counts is None:
         counts = torch.empty((nq, 2), dtype=torch.int32, device=dev)
     _chk_vec(counts, torch.int32, 2 * nq, "counts", dev)
@@ -2266,6 +2307,8 @@ def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c
     if _is_gpu(q_prof):
         h = native.hip()
         need = int(h.place_workspace_bytes(nq, nc, len(ks)))
+        if shortlist is not None:
+            need = int(h.shortlist_workspace_bytes(nq, skw["shortlist_nnz"], nc, 1))
         if ws is None:
             ws = torch.empty(need, dtype=torch.uint8, device=dev)
         _chk_vec(ws, torch.uint8, need, "ws", dev)
@@ -2278,6 +2321,7 @@ def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c
         return PlaceStats(counts, rec, ks, nq, done)
     _check(ws is None, "fm_place: the workspace is a GPU argument")
     skw.pop("seen_nnz", None)
+    skw.pop("shortlist_nnz", None)
     native.cpu().place(threads=threads, **kw, **skw)
     native.cpu().place_metrics(n=nq, counts=_p(counts), cutoffs=list(ks), rec=_p(rec))
     return PlaceStats(counts, rec, ks, nq)

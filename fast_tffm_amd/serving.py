@@ -227,27 +227,31 @@ class ServingModel:
         pred, prof, bias = self._profile(candidate_lines)
         return CandidateIndex(prof, pred - bias if bias is not None else pred)
 
-    def recommend(self, data_lines, candidates, top: int = 10, seen=None) -> tuple[np.ndarray, np.ndarray]:
+    def recommend(self, data_lines, candidates, top: int = 10, seen=None,
+                  shortlist=None) -> tuple[np.ndarray, np.ndarray]:
         """``(idx [B, top] int32, score [B, top] fp32)``: for every context line the ``top`` candidates of
         greatest score of the context's and the candidate's features taken together, best first, equal scores
         by ascending candidate number; -1 / -inf past the number of candidates (``ops.kernels.fm_topk``).
         ``candidates``: lines in the same format, or the ``index`` of them.  ``seen``: per line a list of the
-        candidate numbers to leave out (any order, duplicates allowed)."""
+        candidate numbers to leave out (any order, duplicates allowed).  ``shortlist``: per line a list of the only
+        candidate numbers to rank, e.g. what a retrieval stage handed over (not together with ``seen``)."""
         from .ops import kernels as Kn
 
         ci = candidates if isinstance(candidates, CandidateIndex) else self.index(candidates)
         pred, prof, _ = self._profile(data_lines)
         sn = None if seen is None else Kn.seen_lists(seen, len(ci), prof.device)
-        idx, score = Kn.fm_topk(prof, pred, ci.prof, ci.base, int(top), seen=sn)
+        sl = None if shortlist is None else Kn.seen_lists(shortlist, len(ci), prof.device)
+        idx, score = Kn.fm_topk(prof, pred, ci.prof, ci.base, int(top), seen=sn, shortlist=sl)
         return idx.cpu().numpy(), score.cpu().numpy()
 
 
-    def place(self, data_lines, candidates, targets, cutoffs=(10,), seen=None):
+    def place(self, data_lines, candidates, targets, cutoffs=(10,), seen=None, shortlist=None):
         """The place of every context line's held-out candidate among all candidates, by ``recommend``'s score:
         ``targets`` one candidate number (or -1: none) per line, ``cutoffs`` 1 to 4 ascending integers in [1, 4096].
         Returns the lazy record of ``ops.kernels.fm_place`` (``counts()``, ``hit(k)``, ``ndcg(k)``, ``mrr(k)``,
         ``mean_place()``).  ``candidates``: lines, or the ``index`` of them.  ``seen``: as in ``recommend``; a
-        line's listed candidates other than its target do not compete."""
+        line's listed candidates other than its target do not compete.  ``shortlist``: as in ``recommend``; a line's
+        target competes with its listed candidates alone (sampled-negative evaluation)."""
         from .ops import kernels as Kn
 
         ci = candidates if isinstance(candidates, CandidateIndex) else self.index(candidates)
@@ -256,7 +260,9 @@ class ServingModel:
         if t.numel() and (int(t.min()) < -1 or int(t.max()) >= len(ci)):
             raise ValueError(f"place: targets must be in [-1, {len(ci)})")
         sn = None if seen is None else Kn.seen_lists(seen, len(ci), prof.device)
-        return Kn.fm_place(prof, pred, ci.prof, ci.base, t.to(torch.int32).to(prof.device), cutoffs, seen=sn)
+        sl = None if shortlist is None else Kn.seen_lists(shortlist, len(ci), prof.device)
+        return Kn.fm_place(prof, pred, ci.prof, ci.base, t.to(torch.int32).to(prof.device), cutoffs, seen=sn,
+                           shortlist=sl)
 
 
 class CandidateIndex:

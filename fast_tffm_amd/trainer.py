@@ -722,7 +722,12 @@ class Trainer:
         any order, an empty line for none) ``<file>_recommend`` leaves each context's list out, the places are
         taken among the candidates it has not seen (its own target always competes), and the printed line ends
         with `` seen E``, the file's list entries without duplicates.  Multi-rank runs deal the lists with their
-        contexts."""
+        contexts.
+
+        With ``[Predict] recommend_shortlist_files`` (the same line format; not together with the seen files)
+        every context is ranked and placed within its own list (``FactorizationMachine.recommend`` / ``.place``
+        with ``shortlist``; its target competes whether or not it is listed), and the printed line ends with
+        `` shortlist E``."""
         from .ops import kernels as K
 
         c = self.cfg
@@ -753,12 +758,17 @@ class Trainer:
                 lists = _read_seen(c.recommend_seen_files[fi], b.B, cands.B)
                 seen = K.seen_lists(lists[self.rank::self.world], cands.B, self.device)
                 tail = " seen %d" % sum(len(s) for s in lists)
-            idx, score = self.model.recommend(mine, index, top, seen=seen)
+            kw = dict(seen=seen)  # (without either key: the call as it always was)
+            if c.recommend_shortlist_files:
+                lists = _read_seen(c.recommend_shortlist_files[fi], b.B, cands.B)
+                kw = dict(shortlist=K.seen_lists(lists[self.rank::self.world], cands.B, self.device))
+                tail = " shortlist %d" % sum(len(s) for s in lists)
+            idx, score = self.model.recommend(mine, index, top, **kw)
             part = (idx.cpu().numpy(), score.cpu().numpy())
             if c.recommend_target_files:
                 targets = _read_targets(c.recommend_target_files[fi], b.B, cands.B)
                 t_mine = torch.from_numpy(targets[self.rank::self.world].copy()).to(self.device)
-                part += (self.model.place(mine, index, t_mine, cutoffs, seen=seen).counts().cpu().numpy(),)
+                part += (self.model.place(mine, index, t_mine, cutoffs, **kw).counts().cpu().numpy(),)
             parts = [part]
             if self.world > 1:
                 parts = [None] * self.world
@@ -814,8 +824,8 @@ def _read_targets(path: str, lines: int, candidates: int) -> np.ndarray:
 
 
 def _read_seen(path: str, lines: int, candidates: int) -> list:
-    """The lists of a ``recommend_seen_files`` file: per context line the sorted distinct candidate line numbers
-    in [0, candidates) it names (whitespace-separated, any order; an empty line: none)."""
+    """The lists of a ``recommend_seen_files`` / ``recommend_shortlist_files`` file: per context line the sorted
+    distinct candidate line numbers in [0, candidates) it names (whitespace-separated, any order; empty: none)."""
     out = []
     with open(path) as f:
         for n, text in enumerate(f, 1):
