@@ -57,7 +57,10 @@ Extensions (new keys, all optional):
                 recommend_target_files = <files> (one integer per line, parallel to predict_files: the 0-based
                                 line of the context's held-out candidate in ``recommend --candidates FILE``, or
                                 -1 for none; ``recommend`` then also reports hit@K, ndcg@K, mrr@K and the mean
-                                place over all candidates and writes <file>_places; K: rank_cutoffs, else --top),
+                                place over all candidates and writes <file>_places; K: rank_cutoffs, else --top;
+                                a line may hold several whitespace-separated candidate lines, the context's
+                                held-out set: the report is then recall@K, ndcg@K, precision@K over the contexts
+                                with a target, and <file>_places holds ``target greater equal`` per target),
                 recommend_seen_files = <files> (parallel to predict_files: line i holds the whitespace-separated
                                 0-based candidate lines context i has already seen, in any order, an empty line for
                                 none; ``recommend`` then leaves them out of <file>_recommend and of the places),

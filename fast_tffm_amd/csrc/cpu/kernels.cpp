@@ -1074,6 +1074,78 @@ bool place_metrics(long long n, const int* counts, const int* k, int nk, void* r
   return true;
 }
 
+void place_multi(long long nq, long long nc, int Kp, const float* Q, long long q_stride, const float* C,
+                 long long c_stride, const float* qb, const float* cb, const int* target_off, const int* target_idx,
+                 int* counts, int threads, const int* seen_off, const int* seen_idx) {
+  set_threads(threads);
+  std::vector<int> cols;  // pi(Kp)
+  topk::for_each_col(Kp, [&](int c) { cols.push_back(c); });
+#pragma omp parallel
+  {
+    std::vector<float> qv(cols.size()), s(nc);
+    std::vector<char> out(nc);  // 1: the candidate does not compete for this context
+#pragma omp for schedule(dynamic, 1)
+    for (long long q = 0; q < nq; ++q) {
+      const int t0 = target_off[q], t1 = target_off[q + 1];
+      if (t1 <= t0) continue;
+      const float* qr = Q + q * q_stride;
+      for (size_t i = 0; i < cols.size(); ++i) qv[i] = qr[cols[i]];
+      for (long long c = 0; c < nc; ++c) {  // the context's scores, once
+        const float* cr = C + c * c_stride;
+        float dot = 0.f;
+        for (size_t i = 0; i < cols.size(); ++i) dot = std::fmaf(qv[i], cr[cols[i]], dot);
+        volatile float base = qb[q] + cb[c];  // (two additions as written, then + 0.f: topk's score)
+        volatile float sum = base + dot;
+        s[c] = sum + 0.f;
+      }
+      std::fill(out.begin(), out.end(), 0);
+      if (seen_off)
+        for (int p = seen_off[q]; p < seen_off[q + 1]; ++p)
+          if (seen_idx[p] >= 0 && seen_idx[p] < nc) out[seen_idx[p]] = 1;
+      for (int p = t0; p < t1; ++p)  // (a context's own targets compete even when they are listed)
+        if (target_idx[p] >= 0 && target_idx[p] < nc) out[target_idx[p]] = 0;
+      for (int p = t0; p < t1; ++p) {
+        const int t = target_idx[p] < 0 ? 0 : target_idx[p] >= nc ? (int)(nc - 1) : target_idx[p];
+        const float st = s[t];
+        int gt = 0, eq = 0;
+        for (long long c = 0; c < nc; ++c) {
+          gt += !out[c] && s[c] > st;
+          eq += !out[c] && s[c] == st;
+        }
+        counts[2 * p] = gt;
+        counts[2 * p + 1] = eq;
+      }
+    }
+  }
+}
+
+bool place_multi_metrics(long long n, const int* counts, const int* off, const int* k, int nk, void* rec) {
+  if (!rank_cutoffs_ok(k, nk)) return false;
+  static const std::vector<double> tab = [] {
+    std::vector<double> t(kRankMaxCutoff + 1);
+    rank_dcg_table(t.data());
+    return t;
+  }();
+  long long words[3] = {0, 0, 0};  // ranked contexts, entries, sum of a + b
+  double sums[3 * kRankMaxCutoffs] = {};
+  for (long long q0 = 0; q0 < n; q0 += place::kMetricTile) {
+    double tile[3 * kRankMaxCutoffs] = {}, term[3 * kRankMaxCutoffs];
+    const long long q1 = std::min(n, q0 + place::kMetricTile);
+    for (long long q = q0; q < q1; ++q) {
+      const long long T = (long long)off[q + 1] - off[q];
+      if (T <= 0) continue;
+      ++words[0];
+      words[1] += T;
+      words[2] += place::multi_terms(counts + 2 * (long long)off[q], T, k, nk, tab.data(), term);
+      for (int c = 0; c < 3 * nk; ++c) tile[c] += term[c];
+    }
+    for (int c = 0; c < 3 * nk; ++c) sums[c] += tile[c];
+  }
+  std::memcpy(rec, words, 24);
+  std::memcpy(static_cast<char*>(rec) + 24, sums, sizeof(double) * 3 * nk);
+  return true;
+}
+
 void pairs(int B, const int* offsets, const int* rows, const float* vals, const void* v, long long v_stride, int Kp,
            int dtype, int top, int* first, int* second, float* value, int* count, int threads) {
   set_threads(threads);

@@ -55,6 +55,19 @@ void place(long long nq, long long nc, int Kp, const float* Q, long long q_strid
 // of 1024 contexts in context order, the tiles in tile order, as the GPU does.  False: bad cutoffs.
 bool place_metrics(long long n, const int* counts, const int* k, int nk, void* rec);
 
+// Several targets per context (hip/fm_place_multi.hip: same definition, word for word): target_off [nq + 1] /
+// target_idx [nnz] are CSR lists, ascending within a context; counts[p] = (greater, equal) of entry p among all
+// candidates, or with seen lists among those outside E_q \ T_q.  A context's scores once, then its entries.
+void place_multi(long long nq, long long nc, int Kp, const float* Q, long long q_stride, const float* C,
+                 long long c_stride, const float* qb, const float* cb, const int* target_off, const int* target_idx,
+                 int* counts, int threads, const int* seen_off = nullptr, const int* seen_idx = nullptr);
+
+// The record of n contexts whose entries' (greater, equal) are counts[off[q] .. off[q + 1]) (../place_order.h:
+// multi_terms): rec[3 + 3 nk] 64-bit words = ranked contexts, entries, sum of a + b (int64), then the recall, ndcg,
+// precision sums per cutoff (fp64), added per tile of 1024 contexts in context order, the tiles in tile order, as
+// the GPU does.  False: bad cutoffs.
+bool place_multi_metrics(long long n, const int* counts, const int* off, const int* k, int nk, void* rec);
+
 // The `top` strongest pairs of every example (hip/fm_pairs.hip: same definition, bit for bit): p_jl = (x_j x_l) *
 // fmaf chain over pi(Kp) for j < l, greatest |p| first, equal |p| by ascending (j, l); first / second = -1 and
 // value = 0 past the example's pairs, count = -1 for an example longer than pairs::kMaxN (../pairs_key.h).

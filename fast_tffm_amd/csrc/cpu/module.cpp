@@ -411,6 +411,27 @@ PYBIND11_MODULE(_fm_cpu, m) {
           throw std::invalid_argument("place_metrics: 1 to 4 strictly ascending cutoffs in [1, 4096]");
       },
       py::arg("n"), py::arg("counts"), py::arg("cutoffs"), py::arg("rec"));
+  m.attr("PLACE_SEGMENT") = fm::place::kSegment;
+  m.def(
+      "place_multi",
+      [](long long nq, long long nc, int Kp, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb, u64 cb,
+         u64 target_off, u64 target_idx, u64 counts, int threads, u64 seen_off, u64 seen_idx) {
+        py::gil_scoped_release nogil;
+        fm::cpu::place_multi(nq, nc, Kp, P<const float>(q), q_stride, P<const float>(c), c_stride, P<const float>(qb),
+                             P<const float>(cb), P<const int>(target_off), P<const int>(target_idx), P<int>(counts),
+                             threads, P<const int>(seen_off), P<const int>(seen_idx));
+      },
+      py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
+      py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("target_off"), py::arg("target_idx"),
+      py::arg("counts"), py::arg("threads"), py::arg("seen_off") = 0, py::arg("seen_idx") = 0);
+  m.def(
+      "place_multi_metrics",
+      [](long long n, u64 counts, u64 off, const std::vector<int>& cutoffs, u64 rec) {
+        if (!fm::cpu::place_multi_metrics(n, P<const int>(counts), P<const int>(off), cutoffs.data(),
+                                          (int)cutoffs.size(), P<void>(rec)))
+          throw std::invalid_argument("place_metrics: 1 to 4 strictly ascending cutoffs in [1, 4096]");
+      },
+      py::arg("n"), py::arg("counts"), py::arg("off"), py::arg("cutoffs"), py::arg("rec"));
 
   m.def(
       "dedup",

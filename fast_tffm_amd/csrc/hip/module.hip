@@ -37,6 +37,7 @@ using u64 = std::uintptr_t;
 #include "fm_place.hip"
 #include "fm_seen.hip"
 #include "fm_shortlist.hip"
+#include "fm_place_multi.hip"
 #include "group_loss.hip"
 #include "group_walk.hip"
 #include "group_pair.hip"
@@ -262,6 +263,45 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       },
       py::arg("n"), py::arg("counts"), py::arg("cutoffs"), py::arg("rec"), py::arg("ws"), py::arg("ws_bytes"),
       py::arg("stream"));
+
+  m.attr("PLACE_SEGMENT") = fm::place::kSegment;
+  m.def("place_multi_workspace_bytes", &fm::place_multi_workspace_bytes, py::arg("nq"), py::arg("nc"),
+        py::arg("nnz"), py::arg("nk"));
+  m.def("place_multi_metrics_workspace_bytes", &fm::place_multi_metrics_workspace_bytes, py::arg("n"),
+        py::arg("nk"));
+  m.def(
+      "place_multi",  // several targets per context (fm_place_multi.hip): counts [nnz, 2] and the record [3 + 3 nk]
+      [](long long nq, long long nc, int Kp, u64 q, long long q_stride, u64 c, long long c_stride, u64 qb, u64 cb,
+         u64 target_off, u64 target_idx, long long nnz, const std::vector<int>& cutoffs, u64 counts, u64 rec, u64 ws,
+         size_t ws_bytes, u64 stream, u64 seen_off, u64 seen_idx, int seen_nnz) {
+        fm::MultiArgs a{};
+        a.nq = nq; a.nc = nc; a.nnz = nnz; a.Kp = Kp; a.Q = P<const float>(q); a.q_stride = q_stride;
+        a.C = P<const float>(c); a.c_stride = c_stride; a.qb = P<const float>(qb); a.cb = P<const float>(cb);
+        a.off = P<const int>(target_off); a.idx = P<const int>(target_idx); a.counts = P<int>(counts);
+        const fm::SeenArgs sn{P<const int>(seen_off), P<const int>(seen_idx), seen_nnz};
+        const int rc = fm::launch_place_multi(a, cutoffs.data(), (int)cutoffs.size(), P<void>(rec), P<void>(ws),
+                                              ws_bytes, S(stream), seen_off ? &sn : nullptr);
+        if (rc == -2) throw std::runtime_error("place: workspace too small");
+        if (rc == -7) throw std::invalid_argument("place: 1 to 4 strictly ascending cutoffs in [1, 4096]");
+        check(rc, "fm_place (several targets)");
+      },
+      py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("q"), py::arg("q_stride"), py::arg("c"),
+      py::arg("c_stride"), py::arg("qb"), py::arg("cb"), py::arg("target_off"), py::arg("target_idx"),
+      py::arg("nnz"), py::arg("cutoffs"), py::arg("counts"), py::arg("rec"), py::arg("ws"), py::arg("ws_bytes"),
+      py::arg("stream"), py::arg("seen_off") = 0, py::arg("seen_idx") = 0, py::arg("seen_nnz") = 0);
+  m.def(
+      "place_multi_metrics",  // the reduce pass of fm_place_multi.hip alone: n contexts' entries in counts [nnz, 2]
+      [](long long n, long long nnz, u64 counts, u64 off, const std::vector<int>& cutoffs, u64 rec, u64 ws,
+         size_t ws_bytes, u64 stream) {
+        const int rc = fm::launch_place_multi_metrics(P<const int>(counts), P<const int>(off), n, nnz, cutoffs.data(),
+                                                      (int)cutoffs.size(), P<void>(rec), P<void>(ws), ws_bytes,
+                                                      S(stream));
+        if (rc == -2) throw std::runtime_error("place_metrics: workspace too small");
+        if (rc == -7) throw std::invalid_argument("place_metrics: 1 to 4 strictly ascending cutoffs in [1, 4096]");
+        check(rc, "place_metrics (several targets)");
+      },
+      py::arg("n"), py::arg("nnz"), py::arg("counts"), py::arg("off"), py::arg("cutoffs"), py::arg("rec"),
+      py::arg("ws"), py::arg("ws_bytes"), py::arg("stream"));
 
   m.def(
       "seg_index",

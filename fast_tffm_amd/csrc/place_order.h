@@ -54,5 +54,41 @@ FM_TOPK_HD inline long long terms(int greater, int equal, const int* k, int nk, 
   return lo_r + hi_r + 1;
 }
 
+// ---- several targets per context (hip/fm_place_multi.hip) -------------------------------------------
+// A context's ascending target list is cut into segments of at most kSegment entries; one row of the count pass is
+// one (context, segment), so T targets own ceil(T / kSegment) rows and at most nq + nnz / kSegment rows exist.
+constexpr int kSegment = 32;
+FM_TOPK_HD inline long long segments(long long T) { return (T + kSegment - 1) / kSegment; }
+inline long long multi_rows_max(long long nq, long long nnz) { return nq + nnz / kSegment; }
+
+// The record: 3 + 3 nk 64-bit words: [ranked contexts, entries, sum of a + b over the entries (int64); then per
+// cutoff the sums of recall, ndcg, precision over the ranked contexts (fp64)].
+FM_TOPK_HD inline int multi_rec_words(int nk) { return 3 + 3 * nk; }
+
+// The terms of one ranked context from its T >= 1 (greater, equal) pairs in ascending target order: entry t holds
+// the places a = greater + 1 .. b = greater + equal, the context's hits and DCG at k are the sums over its entries
+// of (min(b, k) - min(a - 1, k)) / equal and (D[min(b, k)] - D[min(a - 1, k)]) / equal -- rank_metrics' expectation
+// under uniform tie-breaking with label 1 on the targets -- added in fp64 in entry order.  out[3 i .. 3 i + 2] =
+// recall, ndcg, precision at k[i].  Returns the sum of a + b.
+FM_TOPK_HD inline long long multi_terms(const int* counts, long long T, const int* k, int nk, const double* D,
+                                        double* out) {
+  long long ab = 0;
+  for (int i = 0; i < nk; ++i) {
+    double hits = 0.0, dcg = 0.0;
+    for (long long t = 0; t < T; ++t) {
+      const long long lo_r = counts[2 * t], hi_r = lo_r + counts[2 * t + 1];
+      const double len = (double)counts[2 * t + 1];
+      const int lo = lo_r < k[i] ? (int)lo_r : k[i], hi = hi_r < k[i] ? (int)hi_r : k[i];
+      hits += (double)(hi - lo) / len;
+      dcg += (D[hi] - D[lo]) / len;
+      if (i == 0) ab += lo_r + hi_r + 1;
+    }
+    out[3 * i] = hits / (double)T;
+    out[3 * i + 1] = dcg / D[T < k[i] ? (int)T : k[i]];
+    out[3 * i + 2] = hits / (double)k[i];
+  }
+  return ab;
+}
+
 }  // namespace place
 }  // namespace fm

@@ -855,7 +855,10 @@ class FactorizationMachine:
         [1, 4096]; the lazy record of ``K.fm_place`` (``counts``, ``hit`` / ``ndcg`` / ``mrr`` per cutoff,
         ``mean_place``).  ``candidates``: a ``Batch`` or the ``(pred, S)`` pair of one, as in ``recommend``.
         ``seen``: as in ``recommend``; a context's listed candidates other than its target do not compete.
-        ``shortlist``: as in ``recommend``; a context's target competes with its listed candidates alone."""
+        ``shortlist``: as in ``recommend``; a context's target competes with its listed candidates alone.
+        ``target`` may also be the ``(target_offsets, target_idx)`` pair of ``K.seen_lists``, per context its set of
+        held-out candidates: the record is then a ``K.PlaceMultiStats`` (``recall`` / ``ndcg`` / ``precision`` per
+        cutoff; not with ``shortlist``)."""
         c_pred, c_prof = self.profile(candidates) if isinstance(candidates, Batch) else candidates
         q_pred, q_prof = self.profile(contexts)
         c_base = c_pred - self.gbias if self.gbias is not None else c_pred

@@ -2202,17 +2202,86 @@ class PlaceStats:
         return ab / (2 * ranked) if ranked else float("nan")
 
 
+PLACE_SEGMENT = 32   # targets per row of the count pass with several targets per context (csrc/place_order.h)
+
+
+class PlaceMultiStats:
+    """The record of one ``fm_place`` / ``place_metrics`` call with several targets per context, on the op's device:
+    ``counts`` (``[nnz, 2]`` int32, ``(greater, equal)`` per entry in entry order -- context, then ascending target)
+    and ``rec``, ``3 + 3 nk`` 64-bit words ``[ranked contexts, entries, sum of a + b over the entries (int64); per
+    cutoff the sums of recall, ndcg, precision over the ranked contexts (fp64)]``.  Read like ``PlaceStats``."""
+
+    __slots__ = ("_counts", "rec", "cutoffs", "n", "done")
+
+    def __init__(self, counts: torch.Tensor, rec: torch.Tensor, cutoffs: tuple, n: int,
+                 done: "torch.cuda.Event | None" = None):
+        self._counts, self.rec, self.cutoffs, self.n, self.done = counts, rec, cutoffs, n, done
+
+    def counts(self) -> torch.Tensor:
+        """The ``[nnz, 2]`` int32 ``(greater, equal)`` tensor on the op's device, once the chain has finished."""
+        if self.done is not None:
+            self.done.synchronize()
+        return self._counts
+
+    def stats(self) -> tuple:
+        """(ranked contexts, entries, sum of a + b, the ``3 nk`` sums ``recall, ndcg, precision`` per cutoff as
+        floats) on the host."""
+        if self.done is not None:
+            self.done.synchronize()
+        r = self.rec.cpu()
+        i = r.tolist()
+        return i[0], i[1], i[2], r.view(torch.float64).tolist()[3:]
+
+    def ranked(self) -> int:
+        """Contexts with at least one target (the ones the means run over)."""
+        return self.stats()[0]
+
+    def entries(self) -> int:
+        """Targets of all contexts together."""
+        return self.stats()[1]
+
+    def _mean(self, k: int, which: int) -> float:
+        if isinstance(k, bool) or not isinstance(k, int):
+            raise ValueError(f"fm_place: a cutoff is an integer, got {k!r}")
+        if k not in self.cutoffs:
+            raise KeyError(f"fm_place: cutoff {k} is not one of this call's {self.cutoffs}")
+        ranked, _, _, sums = self.stats()
+        return sums[3 * self.cutoffs.index(k) + which] / ranked if ranked else float("nan")
+
+    def recall(self, k: int) -> float:
+        """Mean over the ranked contexts of the expected share of a context's targets among the first ``k``; NaN
+        without a ranked context."""
+        return self._mean(k, 0)
+
+    def ndcg(self, k: int) -> float:
+        """Mean NDCG@k with gain 1 on the targets (ideal: the targets first); NaN as ``recall``."""
+        return self._mean(k, 1)
+
+    def precision(self, k: int) -> float:
+        """Mean over the ranked contexts of the expected targets among the first ``k``, over ``k``; NaN as
+        ``recall``."""
+        return self._mean(k, 2)
+
+    def mean_place(self) -> float:
+        """Mean of ``(a + b) / 2`` over all entries (place 1 is best); NaN without an entry."""
+        _, entries, ab, _ = self.stats()
+        return ab / (2 * entries) if entries else float("nan")
+
+
 def place_plan(nq: int, nc: int) -> tuple[int, int]:
     """``(slab, parts)`` of an ``fm_place`` call on the GPU: the candidates per slab and the partial counts per
     query (csrc/place_order.h; a pure function of the sizes, the same from the host module)."""
     return tuple(native.cpu().place_plan(int(nq), int(nc)))
 
 
-def place_workspace(nq: int, nc: int, ncut: int, device: torch.device) -> torch.Tensor:
+def place_workspace(nq: int, nc: int, ncut: int, device: torch.device, entries: int | None = None) -> torch.Tensor:
     """Device scratch of ``fm_place`` with ``ncut`` cutoffs (GPU): s_t, the ranked flags, the slabs' partial counts
-    and the metric tiles."""
-    return torch.empty(int(native.hip().place_workspace_bytes(int(nq), int(nc), int(ncut))), dtype=torch.uint8,
-                       device=device)
+    and the metric tiles.  ``entries``: the call takes a target pair of that many entries together -- the row
+    table, the sorted segments and the entries' partial counts."""
+    h = native.hip()
+    need = (h.place_workspace_bytes(int(nq), int(nc), int(ncut)) if entries is None else
+            h.place_multi_workspace_bytes(int(nq), int(nc), int(entries), int(ncut)))
+    return torch.empty(int(need), dtype=torch.uint8, device=device)
 
 
 def _place_cutoffs(cutoffs) -> tuple:
@@ -2222,16 +2291,50 @@ def _place_cutoffs(cutoffs) -> tuple:
         raise ValueError(str(e).replace("rank_metrics", "fm_place")) from None
 
 
-def place_metrics(counts: torch.Tensor, cutoffs=(10,)) -> PlaceStats:
+def _place_multi_metrics(counts: torch.Tensor, off: torch.Tensor, ks: tuple) -> PlaceMultiStats:
+    """The reduce pass over ``counts [nnz, 2]`` cut into contexts by ``off [n + 1]`` (checked by the caller)."""
+    dev = counts.device
+    n, nnz = off.numel() - 1, counts.shape[0]
+    nw = 3 + 3 * len(ks)
+    if n == 0:  # (a host record: nothing is launched)
+        return PlaceMultiStats(counts, torch.zeros(nw, dtype=torch.int64), ks, 0)
+    rec = torch.empty(nw, dtype=torch.int64, device=dev)
+    if _is_gpu(counts):
+        h = native.hip()
+        need = int(h.place_multi_metrics_workspace_bytes(n, len(ks)))
+        ws = torch.empty(need, dtype=torch.uint8, device=dev) if need else None
+        h.place_multi_metrics(n=n, nnz=nnz, counts=_p(counts), off=_p(off), cutoffs=list(ks), rec=_p(rec), ws=_p(ws),
+                              ws_bytes=need, stream=_stream(counts))
+        done = None
+        if not torch.cuda.is_current_stream_capturing():
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(dev))
+        return PlaceMultiStats(counts, rec, ks, n, done)
+    native.cpu().place_multi_metrics(n=n, counts=_p(counts), off=_p(off), cutoffs=list(ks), rec=_p(rec))
+    return PlaceMultiStats(counts, rec, ks, n)
+
+
+def place_metrics(counts: torch.Tensor, cutoffs=(10,), offsets: torch.Tensor | None = None):
     """The reduce pass of ``fm_place`` alone, on ``counts``' device: the record of ``[n, 2]`` int32 ``(greater,
     equal)`` rows -- e.g. the counts several ranks gathered.  A row with ``equal <= 0`` is unranked.  fp64 sums per
-    tile of 1024 contexts in context order, the tiles in tile order: the same bits on both devices."""
+    tile of 1024 contexts in context order, the tiles in tile order: the same bits on both devices.
+
+    ``offsets``: int32 ``[n + 1]`` from 0 to ``counts``' rows, not decreasing -- the rows are the entries of ``n``
+    contexts with several targets each (``fm_place`` with a target pair), every ``equal >= 1``, and the result is
+    a ``PlaceMultiStats``."""
     ks = _place_cutoffs(cutoffs)
     dev = counts.device
     _check(counts.dim() == 2 and counts.shape[1] == 2, "counts: expected [n, 2]")
     n = counts.shape[0]
     _chk_vec(counts, torch.int32, 2 * n, "counts", dev)
     _check(n < 2**31, "place_metrics: n must be below 2^31")
+    if offsets is not None:
+        _chk_vec(offsets, torch.int32, None, "offsets", dev)
+        _check(offsets.numel() >= 1, "offsets: expected [n + 1]")
+        if not _is_gpu(offsets) or (_DEBUG and not torch.cuda.is_current_stream_capturing()):
+            _check(int(offsets[0]) == 0 and int(offsets[-1]) == n, f"offsets: must run from 0 to {n} (counts' rows)")
+            _check(bool((offsets[1:] >= offsets[:-1]).all()), "offsets: must not decrease")
+        return _place_multi_metrics(counts, offsets, ks)
     nw = 2 + 3 * len(ks)
     if n == 0:  # (a host record: nothing is launched)
         return PlaceStats(counts, torch.zeros(nw, dtype=torch.int64), ks, 0)
@@ -2280,7 +2383,22 @@ def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c
     target always competes, listed or not, an empty list gives ``(0, 1)`` -- and a query with target ``-1`` stays
     all zeros.  GPU: the target pass, the walk over the lists (hip/fm_shortlist.hip) and the reduce pass; the count
     pass over the catalogue is not launched (``ws``: a reusable ``shortlist_workspace``).  Not together with
-    ``seen``."""
+    ``seen``.
+
+    Several targets per context: ``target`` may also be the pair ``(target_offsets int32 [nq + 1], target_idx int32
+    [nnz])`` -- the layout and checks of ``seen``, built by ``seen_lists`` -- per context its set ``T_q`` of held-out
+    candidates, possibly empty (the context is then unranked).  Every entry ``(q, t)`` gets ``(greater, equal)``
+    among all candidates, the context's other targets included; with ``seen`` among the candidates outside ``E_q \\
+    T_q``.  Returns a lazy ``PlaceMultiStats``: ``counts()`` is ``[nnz, 2]`` in entry order, and ``recall(k)`` /
+    ``ndcg(k)`` / ``precision(k)`` are ``rank_metrics``' values over the catalogue with label 1 on the targets,
+    averaged over the ranked contexts.  GPU: hip/fm_place_multi.hip -- every score is computed once on the matrix
+    cores and placed among its context's sorted target scores through an LDS histogram, instead of once per
+    target (``ws``: ``place_workspace(..., entries=nnz)``).  One thread walks a context's entries in the reduce
+    pass: thousands of targets in one context are correct but slow.  Not with ``shortlist``."""
+    if isinstance(target, (tuple, list)):
+        if shortlist is not None:
+            raise ValueError("fm_place: shortlist with several targets per context is not supported")
+        return _fm_place_multi(q_prof, q_base, c_prof, c_base, target, cutoffs, counts, ws, threads, seen)
     ks = _place_cutoffs(cutoffs)
     dev = q_prof.device
     nq, Kp, q_stride = _chk_profiles(q_prof, q_base, "q", dev)
@@ -2325,6 +2443,50 @@ def fm_place(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c
     native.cpu().place(threads=threads, **kw, **skw)
     native.cpu().place_metrics(n=nq, counts=_p(counts), cutoffs=list(ks), rec=_p(rec))
     return PlaceStats(counts, rec, ks, nq)
+
+
+def _fm_place_multi(q_prof, q_base, c_prof, c_base, target, cutoffs, counts, ws, threads, seen) -> PlaceMultiStats:
+    """``fm_place`` with the pair ``target = (target_offsets, target_idx)``."""
+    ks = _place_cutoffs(cutoffs)
+    dev = q_prof.device
+    nq, Kp, q_stride = _chk_profiles(q_prof, q_base, "q", dev)
+    nc, Kc, c_stride = _chk_profiles(c_prof, c_base, "c", dev)
+    _check(Kp == Kc, f"fm_place: profile widths differ ({Kp} and {Kc})")
+    _check(nc < 2**31 and nq < 2**31, "fm_place: nq and nc must be below 2^31")
+    tkw = _chk_seen(target, nq, nc, dev, "fm_place", "target")
+    nnz = tkw["target_nnz"]
+    _check(nq + nnz // PLACE_SEGMENT < 2**31, "fm_place: too many targets")
+    skw = _chk_seen(seen, nq, nc, dev, "fm_place")
+    if counts is None:
+        counts = torch.empty((nnz, 2), dtype=torch.int32, device=dev)
+    _chk_vec(counts, torch.int32, 2 * nnz, "counts", dev)
+    _check(tuple(counts.shape) == (nnz, 2), "counts: expected [nnz, 2]")
+    if nq == 0 or nc == 0:  # (nc == 0: the checks leave no entry)
+        _check(ws is None or _is_gpu(q_prof), "fm_place: the workspace is a GPU argument")
+        return PlaceMultiStats(counts, torch.zeros(3 + 3 * len(ks), dtype=torch.int64), ks, nq)
+    rec = torch.empty(3 + 3 * len(ks), dtype=torch.int64, device=dev)
+    kw = dict(nq=nq, nc=nc, Kp=Kp, q=_p(q_prof), q_stride=q_stride, c=_p(c_prof), c_stride=c_stride,
+              qb=_p(q_base), cb=_p(c_base), target_off=tkw["target_off"], target_idx=tkw["target_idx"],
+              counts=_p(counts))
+    if _is_gpu(q_prof):
+        h = native.hip()
+        need = int(h.place_multi_workspace_bytes(nq, nc, nnz, len(ks)))
+        if ws is None:
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)
+        _chk_vec(ws, torch.uint8, need, "ws", dev)
+        _check(ws.data_ptr() % 8 == 0, "ws: must be 8-byte aligned")
+        h.place_multi(nnz=nnz, cutoffs=list(ks), rec=_p(rec), ws=_p(ws), ws_bytes=ws.numel(), stream=_stream(q_prof),
+                      **kw, **skw)
+        done = None
+        if not torch.cuda.is_current_stream_capturing():
+            done = torch.cuda.Event()
+            done.record(torch.cuda.current_stream(dev))
+        return PlaceMultiStats(counts, rec, ks, nq, done)
+    _check(ws is None, "fm_place: the workspace is a GPU argument")
+    skw.pop("seen_nnz", None)
+    native.cpu().place_multi(threads=threads, **kw, **skw)
+    native.cpu().place_multi_metrics(n=nq, counts=_p(counts), off=tkw["target_off"], cutoffs=list(ks), rec=_p(rec))
+    return PlaceMultiStats(counts, rec, ks, nq)
 
 
 # ---------------------------------------------------------------------------

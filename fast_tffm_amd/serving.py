@@ -251,11 +251,20 @@ class ServingModel:
         Returns the lazy record of ``ops.kernels.fm_place`` (``counts()``, ``hit(k)``, ``ndcg(k)``, ``mrr(k)``,
         ``mean_place()``).  ``candidates``: lines, or the ``index`` of them.  ``seen``: as in ``recommend``; a
         line's listed candidates other than its target do not compete.  ``shortlist``: as in ``recommend``; a line's
-        target competes with its listed candidates alone (sampled-negative evaluation)."""
+        target competes with its listed candidates alone (sampled-negative evaluation).  ``targets`` may also be a
+        list of lists, per line the candidate numbers held out for it (any order, duplicates collapse, empty: none):
+        the record is then a ``PlaceMultiStats`` (``recall(k)``, ``ndcg(k)``, ``precision(k)``; not with
+        ``shortlist``)."""
         from .ops import kernels as Kn
 
         ci = candidates if isinstance(candidates, CandidateIndex) else self.index(candidates)
         pred, prof, _ = self._profile(data_lines)
+        if len(targets) and not np.isscalar(targets[0]):
+            if shortlist is not None:
+                raise ValueError("place: shortlist with several targets per line is not supported")
+            sn = None if seen is None else Kn.seen_lists(seen, len(ci), prof.device)
+            return Kn.fm_place(prof, pred, ci.prof, ci.base, Kn.seen_lists(targets, len(ci), prof.device), cutoffs,
+                               seen=sn)
         t = torch.as_tensor(np.asarray(targets, dtype=np.int64))
         if t.numel() and (int(t.min()) < -1 or int(t.max()) >= len(ci)):
             raise ValueError(f"place: targets must be in [-1, {len(ci)})")

@@ -716,7 +716,11 @@ class Trainer:
         -1) it also prints ``recommend <file>: contexts N ranked R hit@K v ndcg@K v mrr@K v ... mean_place M`` --
         the held-out candidate's place among all candidates (``FactorizationMachine.place``), K the
         ``rank_cutoffs`` when set, else ``top`` -- and writes ``<file>_places``, one line ``target greater equal``
-        per context.  Multi-rank runs gather the counts and rank 0 reduces them (``K.place_metrics``).
+        per context.  Multi-rank runs gather the counts and rank 0 reduces them (``K.place_metrics``).  A line of a
+        target file may hold several whitespace-separated integers, the context's held-out set (duplicates collapse,
+        ``-1`` alone is none); if one does, the line printed is ``... contexts N ranked R targets T recall@K v
+        ndcg@K v precision@K v ... mean_place M`` and line i of ``<file>_places`` holds a ``target greater equal``
+        triple per target in ascending target order (``-1 0 0`` for none).
 
         With ``[Predict] recommend_seen_files`` (line i: the candidate line numbers context i has already seen, in
         any order, an empty line for none) ``<file>_recommend`` leaves each context's list out, the places are
@@ -767,7 +771,10 @@ class Trainer:
             part = (idx.cpu().numpy(), score.cpu().numpy())
             if c.recommend_target_files:
                 targets = _read_targets(c.recommend_target_files[fi], b.B, cands.B)
-                t_mine = torch.from_numpy(targets[self.rank::self.world].copy()).to(self.device)
+                if isinstance(targets, list):  # (several targets on some line: the pair form)
+                    t_mine = K.seen_lists(targets[self.rank::self.world], cands.B, self.device)
+                else:
+                    t_mine = torch.from_numpy(targets[self.rank::self.world].copy()).to(self.device)
                 part += (self.model.place(mine, index, t_mine, cutoffs, **kw).counts().cpu().numpy(),)
             parts = [part]
             if self.world > 1:
@@ -786,7 +793,29 @@ class Trainer:
                     f.write(" ".join(f"{ci}:{str(np.float32(sc))}" for ci, sc in zip(full_i[i], full_s[i]) if ci >= 0)
                             + "\n")
             written.append(out)
-            if c.recommend_target_files:
+            if c.recommend_target_files and isinstance(targets, list):
+                off = np.zeros(b.B + 1, dtype=np.int32)
+                np.cumsum([len(t) for t in targets], out=off[1:])
+                counts = np.empty((off[-1], 2), dtype=np.int32)
+                for r, p_r in enumerate(parts):  # a rank's entries are those of its contexts, in their order
+                    pos = 0
+                    for i in range(r, b.B, self.world):
+                        counts[off[i]:off[i + 1]] = p_r[2][pos:pos + len(targets[i])]
+                        pos += len(targets[i])
+                ps = K.place_metrics(torch.from_numpy(counts).to(self.device), cutoffs,
+                                     offsets=torch.from_numpy(off).to(self.device))
+                line = "recommend %s: contexts %d ranked %d targets %d" % (path, b.B, ps.ranked(), ps.entries())
+                for kk in cutoffs:
+                    line += " recall@%d %.8f ndcg@%d %.8f precision@%d %.8f" % (kk, ps.recall(kk), kk, ps.ndcg(kk), kk,
+                                                                                ps.precision(kk))
+                self.print(line + " mean_place %.8g" % ps.mean_place() + tail)
+                out = path + "_places"
+                with open(out, "w") as f:
+                    for i, ts in enumerate(targets):
+                        rows = [f"{t} {gt} {eq}" for t, (gt, eq) in zip(ts, counts[off[i]:off[i + 1]])]
+                        f.write((" ".join(rows) if rows else "-1 0 0") + "\n")
+                written.append(out)
+            elif c.recommend_target_files:
                 counts = np.empty((b.B, 2), dtype=np.int32)
                 for r, p_r in enumerate(parts):
                     counts[r::self.world] = p_r[2]
@@ -804,23 +833,27 @@ class Trainer:
         return written
 
 
-def _read_targets(path: str, lines: int, candidates: int) -> np.ndarray:
-    """The int32 targets of a ``recommend_target_files`` file: one integer in [-1, candidates) per context line."""
+def _read_targets(path: str, lines: int, candidates: int):
+    """The targets of a ``recommend_target_files`` file.  Every line holds one integer in [-1, candidates): the int32
+    array of them.  Some line holds several whitespace-separated integers in [0, candidates): a list per context
+    line of its sorted distinct targets (``-1`` alone: none)."""
     out = []
     with open(path) as f:
         for n, text in enumerate(f, 1):
             try:
-                t = int(text.strip())
+                row = [int(tok) for tok in text.split()]
             except ValueError:
-                t = None
-            if t is None or not -1 <= t < candidates:
+                row = None
+            if not row or not all((-1 if len(row) == 1 else 0) <= t < candidates for t in row):
                 raise ValueError(f"{path}, line {n}: expected a candidate line number in [-1, {candidates}), got "
                                  f"{text.strip()!r}")
-            out.append(t)
+            out.append(row)
     if len(out) != lines:
         raise ValueError(f"{path}, line {min(len(out), lines) + 1}: {len(out)} lines but the predict file has "
                          f"{lines} contexts")
-    return np.array(out, dtype=np.int32)
+    if all(len(row) == 1 for row in out):
+        return np.array([row[0] for row in out], dtype=np.int32)
+    return [[] if row == [-1] else sorted(set(row)) for row in out]
 
 
 def _read_seen(path: str, lines: int, candidates: int) -> list:
