@@ -11,8 +11,9 @@ Extensions: --device {auto,cpu,cuda}, --mode {auto,local,shard,dp,dp_dense},
 (exact per-feature attributions of the predict files' scores: ``<file>_contrib`` and
 ``<file>_importance``, with ``--pairs`` every line's strongest feature pairs: ``<file>_pairs`` and
 ``<file>_pair_importance``, trainer.Trainer.explain; the reference has no equivalent), the task
-``recommend CONFIG --candidates FILE [--top N]`` (for every line of the predict files the N best lines of
-FILE by the score of both taken together: ``<file>_recommend``, trainer.Trainer.recommend), the task
+``recommend CONFIG --candidates FILE [--top N] [--diversity LAMBDA [--pool M]]`` (for every line of the predict
+files the N best lines of FILE by the score of both taken together: ``<file>_recommend``, with ``--diversity`` the N
+greedy maximal-marginal-relevance picks from the M best, trainer.Trainer.recommend), the task
 ``evaluate CONFIG`` (loss and ROC AUC of the checkpoint on the labelled predict files and, with ``[Predict]
 predict_group_files``, the grouped AUC and ``<file>_gauc``, with ``rank_cutoffs`` NDCG@k / recall@k /
 precision@k and ``<file>_rank``, with ``auc_interval`` DeLong's standard error and confidence interval of the
@@ -72,6 +73,12 @@ def build_parser() -> argparse.ArgumentParser:
                         "<file>_pair_importance over those pairs")
     p.add_argument("--candidates", default=None, metavar="FILE",
                    help="recommend: the candidates, one per line in the predict files' format")
+    p.add_argument("--diversity", type=float, default=None, metavar="LAMBDA",
+                   help="recommend: re-rank every line's pool by greedy maximal marginal relevance; LAMBDA in "
+                        "[0, 1] weighs relevance against similarity to the picks so far (1: relevance alone)")
+    p.add_argument("--pool", type=int, default=None, metavar="M",
+                   help="recommend --diversity: candidates retrieved per line before re-ranking (--top..128, default "
+                        "min(128, 4 x --top))")
     p.add_argument("--calibrated", action="store_true",
                    help="predict: also write <file>_prob, the calibrated probability of every score (needs the "
                         "calibration.json that 'calibrate' wrote into the checkpoint's directory)")
@@ -85,6 +92,8 @@ def main(argv: list[str] | None = None) -> int:
     args = parser.parse_args(argv)
     if args.task == "recommend" and not args.candidates:
         parser.error("recommend needs --candidates FILE")
+    if args.pool is not None and args.diversity is None:
+        parser.error("--pool needs --diversity")
     from .config import load_config
     from .parallel import dist as fmdist
 
@@ -169,7 +178,8 @@ def main(argv: list[str] | None = None) -> int:
         elif args.task == "explain":
             tr.explain(top=args.top, pairs=args.pairs)
         elif args.task == "recommend":
-            tr.recommend(args.candidates, top=10 if args.top is None else args.top)
+            dkw = {} if args.diversity is None else dict(diversity=args.diversity, pool=args.pool)
+            tr.recommend(args.candidates, top=10 if args.top is None else args.top, **dkw)
         else:
             tr.predict(calibrated=args.calibrated)
     except CalibrationError as e:

@@ -994,6 +994,60 @@ void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q
   }
 }
 
+void diversify(long long nq, long long nc, int Kp, int M, int n, const float* C, long long c_stride,
+               const float* inv, const int* pool_idx, const float* pool_score, float lam, float neg_mu, int* idx,
+               float* score, float* mmr, int threads) {
+  set_threads(threads);
+  std::vector<int> cols;  // pi(Kp)
+  topk::for_each_col(Kp, [&](int c) { cols.push_back(c); });
+  const float ninf = -std::numeric_limits<float>::infinity();
+#pragma omp parallel
+  {
+    std::vector<float> rel(M), pen(M), sv(cols.size());
+    std::vector<char> open(M);
+#pragma omp for schedule(dynamic, 1)
+    for (long long q = 0; q < nq; ++q) {
+      const int* pi = pool_idx + q * M;
+      for (int j = 0; j < M; ++j) {
+        open[j] = pi[j] >= 0 && pi[j] < nc;
+        rel[j] = lam * pool_score[q * M + j];
+        pen[j] = 0.f;
+      }
+      for (int t = 0; t < n; ++t) {
+        uint64_t best = 0;  // the greatest key of the open positions (a key is never 0)
+        for (int j = 0; j < M; ++j) {
+          if (!open[j]) continue;
+          volatile float f = std::fmaf(neg_mu, pen[j], rel[j]);
+          const float m = f + 0.f;  // (-0 becomes +0)
+          uint32_t bits;
+          std::memcpy(&bits, &m, 4);
+          const uint64_t key = topk::make_key(bits, (uint32_t)j);
+          if (key > best) best = key;
+        }
+        const int s = topk::key_index(best);
+        const uint32_t mb = topk::key_score_bits(best);
+        idx[q * n + t] = s < 0 ? -1 : pi[s];
+        score[q * n + t] = s < 0 ? ninf : pool_score[q * M + s];
+        std::memcpy(&mmr[q * n + t], &mb, 4);
+        if (s < 0) continue;  // the pool is used up: the rest of the row is empty too
+        open[s] = 0;
+        const float* sr = C + (long long)pi[s] * c_stride;
+        for (size_t i = 0; i < cols.size(); ++i) sv[i] = sr[cols[i]];
+        const float is = inv[pi[s]];
+        for (int j = 0; j < M; ++j) {
+          if (!open[j]) continue;
+          const float* jr = C + (long long)pi[j] * c_stride;
+          float dot = 0.f;
+          for (size_t i = 0; i < cols.size(); ++i) dot = std::fmaf(jr[cols[i]], sv[i], dot);
+          volatile float one = dot * inv[pi[j]];  // (two roundings, as written)
+          const float sim = one * is;
+          pen[j] = t == 0 || sim > pen[j] ? sim : pen[j];
+        }
+      }
+    }
+  }
+}
+
 void place(long long nq, long long nc, int Kp, const float* Q, long long q_stride, const float* C,
            long long c_stride, const float* qb, const float* cb, const int* target, int* counts, int threads,
            const int* seen_off, const int* seen_idx, const int* short_off, const int* short_idx) {

@@ -40,6 +40,15 @@ void topk(long long nq, long long nc, int Kp, int k, const float* Q, long long q
           const int* seen_off = nullptr, const int* seen_idx = nullptr, const int* short_off = nullptr,
           const int* short_idx = nullptr);
 
+// n greedy MMR picks from every context's pool of M positions (hip/fm_diversify.hip: same definition, bit for bit):
+// sim_jl = (fmaf chain over pi(Kp) of C[a], C[b]) * inv[a] * inv[b] for the candidates a, b of positions j, l;
+// pick the open position of greatest m_j = fmaf(neg_mu, pen_j, lam * pool_score[j]) + 0.f, equal m by lower
+// position, pen_j the greatest sim_js over the picks s so far (0 before the first).  idx / score / mmr [nq, n]:
+// the candidate, its pool score and m; -1 / -inf / -inf once a pool (positions of a candidate in [0, nc)) is used up.
+void diversify(long long nq, long long nc, int Kp, int M, int n, const float* C, long long c_stride,
+               const float* inv, const int* pool_idx, const float* pool_score, float lam, float neg_mu, int* idx,
+               float* score, float* mmr, int threads);
+
 // The place of a held-out candidate among all candidates (hip/fm_place.hip: same definition, word for word):
 // with topk's score s, counts[q] = (#{c : s(q, c) > s(q, t)}, #{c : s(q, c) == s(q, t)}), t = target[q]; a target
 // outside [0, nc) leaves (0, 0): unranked.  With seen lists (as topk's) a query's listed candidates other than its

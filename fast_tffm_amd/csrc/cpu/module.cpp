@@ -384,6 +384,17 @@ PYBIND11_MODULE(_fm_cpu, m) {
       "shortlist_plan",
       [](long long nq, long long nnz, long long nc) { return fm::topk::shortlist_plan(nq, nnz, nc); }, py::arg("nq"),
       py::arg("nnz"), py::arg("nc"));
+  m.def(
+      "diversify",
+      [](long long nq, long long nc, int Kp, int M, int n, u64 c, long long c_stride, u64 inv, u64 pool_idx,
+         u64 pool_score, float lam, float mu, u64 idx, u64 score, u64 mmr, int threads) {
+        py::gil_scoped_release nogil;
+        fm::cpu::diversify(nq, nc, Kp, M, n, P<const float>(c), c_stride, P<const float>(inv), P<const int>(pool_idx),
+                           P<const float>(pool_score), lam, -mu, P<int>(idx), P<float>(score), P<float>(mmr), threads);
+      },
+      py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("M"), py::arg("n"), py::arg("c"), py::arg("c_stride"),
+      py::arg("inv"), py::arg("pool_idx"), py::arg("pool_score"), py::arg("lam"), py::arg("mu"), py::arg("idx"),
+      py::arg("score"), py::arg("mmr"), py::arg("threads"));
 
   m.def(
       "place_plan",

@@ -37,6 +37,7 @@ using u64 = std::uintptr_t;
 #include "fm_place.hip"
 #include "fm_seen.hip"
 #include "fm_shortlist.hip"
+#include "fm_diversify.hip"
 #include "fm_place_multi.hip"
 #include "group_loss.hip"
 #include "group_walk.hip"
@@ -217,6 +218,19 @@ PYBIND11_MODULE(FM_HIP_MODULE, m) {
       py::arg("nnz"), py::arg("nc"));
   m.def("shortlist_workspace_bytes", &fm::shortlist_workspace_bytes, py::arg("nq"), py::arg("nnz"), py::arg("nc"),
         py::arg("k"));
+  m.def(
+      "diversify",  // n greedy MMR picks from every context's pool (fm_diversify.hip): idx / score / mmr [nq, n]
+      [](long long nq, long long nc, int Kp, int M, int n, u64 c, long long c_stride, u64 inv, u64 pool_idx,
+         u64 pool_score, float lam, float mu, u64 idx, u64 score, u64 mmr, u64 stream) {
+        fm::DiversifyArgs a{};
+        a.nq = nq; a.nc = nc; a.Kp = Kp; a.M = M; a.n = n; a.C = P<const float>(c); a.c_stride = c_stride;
+        a.inv = P<const float>(inv); a.pool_idx = P<const int>(pool_idx); a.pool_score = P<const float>(pool_score);
+        a.lam = lam; a.neg_mu = -mu; a.idx = P<int>(idx); a.score = P<float>(score); a.mmr = P<float>(mmr);
+        check(fm::launch_diversify(a, S(stream)), "fm_diversify");
+      },
+      py::arg("nq"), py::arg("nc"), py::arg("Kp"), py::arg("M"), py::arg("n"), py::arg("c"), py::arg("c_stride"),
+      py::arg("inv"), py::arg("pool_idx"), py::arg("pool_score"), py::arg("lam"), py::arg("mu"), py::arg("idx"),
+      py::arg("score"), py::arg("mmr"), py::arg("stream"));
 
   m.def(
       "place_plan",  // (slab, parts) of a place call: candidates per slab, partial counts per query (place_order.h)

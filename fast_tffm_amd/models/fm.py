@@ -832,20 +832,28 @@ class FactorizationMachine:
         return fo.pred, fo.r1
 
     @torch.no_grad()
-    def recommend(self, contexts: Batch, candidates, k: int, seen=None,
-                  shortlist=None) -> tuple[torch.Tensor, torch.Tensor]:
+    def recommend(self, contexts: Batch, candidates, k: int, seen=None, shortlist=None, diversity=None,
+                  pool=None) -> tuple[torch.Tensor, torch.Tensor]:
         """The ``k`` best candidates of every context: ``(idx [B, k] int32, score [B, k] fp32)``, the score of
         the context's and the candidate's features taken together (``K.fm_topk``: greater first, ties by
         ascending candidate, -1 / -inf past the candidate count).  ``candidates``: a ``Batch`` of candidate
         examples, or the ``(pred, S)`` pair ``profile`` returned for one (profile a catalogue once).  ``seen``:
         the ``(seen_offsets, seen_idx)`` pair of ``K.seen_lists``, per context the candidates to leave out.
         ``shortlist``: a pair of the same kind, per context the only candidates to rank (not together with
-        ``seen``)."""
+        ``seen``).  ``diversity``: a number lambda in [0, 1] re-ranks the ``pool`` best (default ``min(128, 4 k)``,
+        capped by the catalogue) by greedy maximal marginal relevance on the cosine of the candidates' ``S``
+        (``K.fm_diversify``; 1: relevance alone) and returns the ``k`` picks in pick order with their scores.
+        ``None``: the plain ranking."""
         c_pred, c_prof = self.profile(candidates) if isinstance(candidates, Batch) else candidates
         q_pred, q_prof = self.profile(contexts)
         c_base = c_pred - self.gbias if self.gbias is not None else c_pred
-        return K.fm_topk(q_prof, q_pred, c_prof, c_base, k, threads=self.cfg.threads, seen=seen,
-                         shortlist=shortlist)
+        if diversity is None:
+            if pool is not None:
+                raise ValueError("recommend: pool needs diversity")
+            return K.fm_topk(q_prof, q_pred, c_prof, c_base, k, threads=self.cfg.threads, seen=seen,
+                             shortlist=shortlist)
+        return K._recommend_diverse(q_prof, q_pred, c_prof, c_base, K.diversify_scale(c_prof), k, diversity, pool,
+                                    threads=self.cfg.threads, seen=seen, shortlist=shortlist)
 
     @torch.no_grad()
     def place(self, contexts: Batch, candidates, target: torch.Tensor, cutoffs=(10,), seen=None,

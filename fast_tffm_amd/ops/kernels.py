@@ -2001,8 +2001,11 @@ def topk_workspace(nq: int, nc: int, k: int, device: torch.device) -> torch.Tens
                        device=device)
 
 
-def _chk_profiles(t: torch.Tensor, base: torch.Tensor, name: str, dev: torch.device) -> tuple[int, int, int]:
-    """Validate a profile matrix [n, Kp] (+ its base scores [n]); returns (n, Kp, row stride)."""
+def _chk_profiles(t: torch.Tensor, base: torch.Tensor, name: str, dev: torch.device,
+                  base_name: str | None = None) -> tuple[int, int, int]:
+    """Validate a profile matrix [n, Kp] (+ its base scores [n], or another per-row vector called ``base_name``);
+    returns (n, Kp, row stride)."""
+    base_name = base_name or f"{name}_base"
     _check(t.dim() == 2, f"{name}_prof: expected [n, Kp]")
     _check(t.dtype == torch.float32, f"{name}_prof: expected {torch.float32}, got {t.dtype}")
     _check(t.device == dev, f"{name}_prof: expected device {dev}, got {t.device}")
@@ -2012,8 +2015,9 @@ def _chk_profiles(t: torch.Tensor, base: torch.Tensor, name: str, dev: torch.dev
     stride = t.stride(0) if n > 1 else Kp  # (the stride of a single row is never used)
     _check(stride >= Kp and stride % 4 == 0, f"{name}_prof: row stride {stride} must be a multiple of 4 >= Kp")
     _check(n == 0 or t.data_ptr() % 16 == 0, f"{name}_prof: base must be 16-byte aligned")
-    _chk_vec(base, torch.float32, n, f"{name}_base", dev)
-    _check(base.numel() == n, f"{name}_base: one base score per profile row")
+    _chk_vec(base, torch.float32, n, base_name, dev)
+    what = "base score" if base_name[-5:] == "_base" else "value"
+    _check(base.numel() == n, f"{base_name}: one {what} per profile row")
     return n, Kp, stride
 
 
@@ -2138,6 +2142,90 @@ def fm_topk(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_
         skw.pop("seen_nnz", None)
         skw.pop("shortlist_nnz", None)
         native.cpu().topk(threads=threads, **kw, **skw)
+    return idx, score
+
+
+# ---------------------------------------------------------------------------
+# diversified recommendations: greedy MMR re-ranking of fm_topk's rows
+# ---------------------------------------------------------------------------
+def diversify_scale(c_prof: torch.Tensor, similarity: str = "cosine") -> torch.Tensor:
+    """The ``c_inv`` of ``fm_diversify`` for a catalogue's profiles ``[nc, Kp]`` (compute it once per catalogue):
+    ``"cosine"``: ``1 / sqrt(sum S^2)`` per row, 0 for a zero row; ``"dot"``: ones, the raw inner product."""
+    _check(similarity in ("cosine", "dot"), f"diversify_scale: similarity is 'cosine' or 'dot', got {similarity!r}")
+    _check(c_prof.dim() == 2 and c_prof.dtype == torch.float32, "diversify_scale: c_prof: expected fp32 [nc, Kp]")
+    if similarity == "dot":
+        return torch.ones(c_prof.shape[0], dtype=torch.float32, device=c_prof.device)
+    norm = c_prof.square().sum(dim=1).sqrt()
+    return torch.where(norm > 0, 1.0 / norm, torch.zeros_like(norm))
+
+
+def _f32(x: float) -> float:
+    return struct.unpack("f", struct.pack("f", x))[0]
+
+
+def fm_diversify(c_prof: torch.Tensor, c_inv: torch.Tensor, pool_idx: torch.Tensor, pool_score: torch.Tensor, n: int,
+                 lam: float, *, out: tuple | None = None,
+                 threads: int = 0) -> tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``n`` diversified picks from every context's pool by greedy maximal marginal relevance
+    (hip/fm_diversify.hip; the reference only scores).
+
+    ``pool_idx`` int32 / ``pool_score`` fp32 ``[nq, M]``, ``1 <= n <= M <= 128``: ``fm_topk``'s two outputs (``-1``:
+    no candidate at that position).  For positions j, l holding candidates a, b: ``sim_jl = (dot * c_inv[a]) *
+    c_inv[b]`` with ``dot`` the fp32 fmaf chain of ``c_prof[a]`` and ``c_prof[b]`` over the columns in the order of
+    csrc/topk_order.h (``c_inv``: ``diversify_scale``).  Pick t takes the unpicked position of greatest ``m_j =
+    fmaf(-(1 - lam), pen_j, lam * pool_score[j]) + 0``, equal ``m`` by lower position, ``pen_j`` the greatest
+    ``sim_js`` over the positions s picked so far (0 for the first pick); ``lam`` in [0, 1], ``1 - lam`` rounded to
+    fp32 once.  Returns ``(idx [nq, n] int32, score [nq, n] fp32, mmr [nq, n] fp32)``: the picked candidates in
+    pick order, their pool scores and the ``m`` they were picked with; ``-1 / -inf / -inf`` once a pool is used up.
+    ``lam = 1`` returns the pool's first ``n``.  The same candidate at two positions is two positions.  Exact fp32 on
+    the matrix cores, bitwise reproducible, bit for bit the same on the CPU.  GPU: current stream, one wave per
+    context, no workspace, no host synchronisation.  ``out``: the three tensors to write.  Scores and profiles are
+    expected to be finite."""
+    dev = c_prof.device
+    nc, Kp, c_stride = _chk_profiles(c_prof, c_inv, "c", dev, "c_inv")
+    _check(pool_idx.dim() == 2 and pool_idx.dtype == torch.int32 and pool_idx.device == dev and
+           pool_idx.is_contiguous(), "pool_idx: expected a contiguous int32 [nq, M] on the profiles' device")
+    nq, M = pool_idx.shape
+    _check(1 <= M <= TOPK_MAX_K, f"fm_diversify: the pool M must be in 1..{TOPK_MAX_K}, got {M}")
+    _check(pool_score.dtype == torch.float32 and pool_score.device == dev and pool_score.is_contiguous() and
+           tuple(pool_score.shape) == (nq, M), "pool_score: expected a contiguous fp32 [nq, M] beside pool_idx")
+    _check(isinstance(n, int) and 1 <= n <= M, f"fm_diversify: n must be in 1..M = {M}, got {n}")
+    _check(0.0 <= float(lam) <= 1.0, f"fm_diversify: lam must be in [0, 1], got {lam}")
+    lam32 = _f32(float(lam))
+    _check(nc < 2**31 and nq < 2**31, "fm_diversify: nq and nc must be below 2^31")
+    if out is None:
+        out = (torch.empty((nq, n), dtype=torch.int32, device=dev),
+               torch.empty((nq, n), dtype=torch.float32, device=dev),
+               torch.empty((nq, n), dtype=torch.float32, device=dev))
+    _check(isinstance(out, (tuple, list)) and len(out) == 3, "fm_diversify: out is the triple (idx, score, mmr)")
+    idx, score, mmr = out
+    _chk_vec(idx, torch.int32, nq * n, "idx", dev)
+    _chk_vec(score, torch.float32, nq * n, "score", dev)
+    _chk_vec(mmr, torch.float32, nq * n, "mmr", dev)
+    _check(all(tuple(t.shape) == (nq, n) for t in out), "idx / score / mmr: expected [nq, n]")
+    if nq == 0:
+        return idx, score, mmr
+    kw = dict(nq=nq, nc=nc, Kp=Kp, M=M, n=n, c=_p(c_prof), c_stride=c_stride, inv=_p(c_inv), pool_idx=_p(pool_idx),
+              pool_score=_p(pool_score), lam=lam32, mu=_f32(1.0 - lam32), idx=_p(idx),
+              score=_p(score), mmr=_p(mmr))
+    if _is_gpu(c_prof):
+        native.hip().diversify(stream=_stream(c_prof), **kw)
+    else:
+        native.cpu().diversify(threads=threads, **kw)
+    return idx, score, mmr
+
+
+def _recommend_diverse(q_prof: torch.Tensor, q_base: torch.Tensor, c_prof: torch.Tensor, c_base: torch.Tensor,
+                       c_inv: torch.Tensor, k: int, diversity: float, pool: int | None = None, *, threads: int = 0,
+                       seen=None, shortlist=None) -> tuple[torch.Tensor, torch.Tensor]:
+    """``fm_topk(k=pool)`` then ``fm_diversify(n=k, lam=diversity)``: ``(idx [nq, k], score [nq, k])``, the picks
+    and their relevance scores (the body of the models' ``recommend(diversity=)``).  ``pool``: the positions
+    retrieved per context, in ``k..128``; ``None``: ``min(128, 4 k)`` capped by the catalogue, at least ``k``."""
+    _check(isinstance(k, int) and 1 <= k <= TOPK_MAX_K, f"recommend: k must be in 1..{TOPK_MAX_K}, got {k}")
+    M = max(k, min(TOPK_MAX_K, 4 * k, c_prof.shape[0])) if pool is None else pool
+    _check(isinstance(M, int) and k <= M <= TOPK_MAX_K, f"recommend: pool must be in k..{TOPK_MAX_K}, got {M}")
+    p_idx, p_score = fm_topk(q_prof, q_base, c_prof, c_base, M, threads=threads, seen=seen, shortlist=shortlist)
+    idx, score, _ = fm_diversify(c_prof, c_inv, p_idx, p_score, k, diversity, threads=threads)
     return idx, score
 
 

@@ -223,25 +223,36 @@ class ServingModel:
 
     def index(self, candidate_lines) -> "CandidateIndex":
         """Profile a catalogue once: the object ``recommend`` takes in place of candidate lines (it keeps
-        every candidate's score less the global bias and its ``S = sum_j x_j v_j`` on the device)."""
+        every candidate's score less the global bias and its ``S = sum_j x_j v_j`` on the device, and from the first
+        ``recommend(diversity=)`` on the reciprocal norm of ``S`` beside them)."""
         pred, prof, bias = self._profile(candidate_lines)
         return CandidateIndex(prof, pred - bias if bias is not None else pred)
 
-    def recommend(self, data_lines, candidates, top: int = 10, seen=None,
-                  shortlist=None) -> tuple[np.ndarray, np.ndarray]:
+    def recommend(self, data_lines, candidates, top: int = 10, seen=None, shortlist=None, diversity=None,
+                  pool=None) -> tuple[np.ndarray, np.ndarray]:
         """``(idx [B, top] int32, score [B, top] fp32)``: for every context line the ``top`` candidates of
         greatest score of the context's and the candidate's features taken together, best first, equal scores
         by ascending candidate number; -1 / -inf past the number of candidates (``ops.kernels.fm_topk``).
         ``candidates``: lines in the same format, or the ``index`` of them.  ``seen``: per line a list of the
         candidate numbers to leave out (any order, duplicates allowed).  ``shortlist``: per line a list of the only
-        candidate numbers to rank, e.g. what a retrieval stage handed over (not together with ``seen``)."""
+        candidate numbers to rank, e.g. what a retrieval stage handed over (not together with ``seen``).
+        ``diversity``: a number lambda in [0, 1] re-ranks every line's ``pool`` best candidates (default
+        ``min(128, 4 top)``, capped by the catalogue) by greedy maximal marginal relevance on the cosine of the
+        candidates' ``S`` (``ops.kernels.fm_diversify``; 1: relevance alone, smaller: more varied) and returns the
+        ``top`` picks in pick order with their scores.  ``None``: the plain ranking."""
         from .ops import kernels as Kn
 
         ci = candidates if isinstance(candidates, CandidateIndex) else self.index(candidates)
         pred, prof, _ = self._profile(data_lines)
         sn = None if seen is None else Kn.seen_lists(seen, len(ci), prof.device)
         sl = None if shortlist is None else Kn.seen_lists(shortlist, len(ci), prof.device)
-        idx, score = Kn.fm_topk(prof, pred, ci.prof, ci.base, int(top), seen=sn, shortlist=sl)
+        if diversity is None:
+            if pool is not None:
+                raise ValueError("recommend: pool needs diversity")
+            idx, score = Kn.fm_topk(prof, pred, ci.prof, ci.base, int(top), seen=sn, shortlist=sl)
+        else:
+            idx, score = Kn._recommend_diverse(prof, pred, ci.prof, ci.base, ci.inv, int(top), diversity, pool,
+                                               seen=sn, shortlist=sl)
         return idx.cpu().numpy(), score.cpu().numpy()
 
 
@@ -277,10 +288,20 @@ class ServingModel:
 class CandidateIndex:
     """Profiles of a candidate catalogue on the serving device (``ServingModel.index``)."""
 
-    __slots__ = ("prof", "base")
+    __slots__ = ("prof", "base", "_inv")
 
     def __init__(self, prof: torch.Tensor, base: torch.Tensor):
-        self.prof, self.base = prof, base
+        self.prof, self.base, self._inv = prof, base, None
+
+    @property
+    def inv(self) -> torch.Tensor:
+        """The reciprocal norm of every profile, ``recommend(diversity=)``'s similarity scale: computed at the first
+        diversified call and kept."""
+        if self._inv is None:
+            from .ops import kernels as Kn
+
+            self._inv = Kn.diversify_scale(self.prof)
+        return self._inv
 
     def __len__(self) -> int:
         return self.prof.shape[0]

@@ -704,7 +704,8 @@ class Trainer:
 
 
     # ------------------------------------------------------------------
-    def recommend(self, candidates: str, top: int = 10) -> list[str]:
+    def recommend(self, candidates: str, top: int = 10, diversity: float | None = None,
+                  pool: int | None = None) -> list[str]:
         """``run.py recommend``: rank the candidates of file ``candidates`` (one per line, the predict files'
         format; the label column is read and ignored) for every line of the predict files.  Writes
         ``<file>_recommend``: line i holds up to ``top`` tokens ``c:score``, best first (equal scores by
@@ -731,12 +732,23 @@ class Trainer:
         With ``[Predict] recommend_shortlist_files`` (the same line format; not together with the seen files)
         every context is ranked and placed within its own list (``FactorizationMachine.recommend`` / ``.place``
         with ``shortlist``; its target competes whether or not it is listed), and the printed line ends with
-        `` shortlist E``."""
+        `` shortlist E``.
+
+        ``diversity`` (``--diversity LAMBDA``, in [0, 1]; ``pool``: ``--pool M``, ``top..128``): ``<file>_recommend``
+        holds every context's ``top`` greedy maximal-marginal-relevance picks from its ``pool`` best candidates, in
+        pick order, each with its relevance score (``FactorizationMachine.recommend`` with ``diversity``).  The
+        places of the target files are taken on relevance as before."""
         from .ops import kernels as K
 
         c = self.cfg
         if not isinstance(top, int) or not 1 <= top <= K.TOPK_MAX_K:
             raise ValueError(f"recommend: --top must be in 1..{K.TOPK_MAX_K}, got {top}")
+        if diversity is None and pool is not None:
+            raise ValueError("recommend: --pool needs --diversity")
+        if diversity is not None and not 0.0 <= diversity <= 1.0:
+            raise ValueError(f"recommend: --diversity must be in [0, 1], got {diversity}")
+        if pool is not None and not top <= pool <= K.TOPK_MAX_K:
+            raise ValueError(f"recommend: --pool must be in --top..{K.TOPK_MAX_K}, got {pool}")
         if not self.restore():
             raise FileNotFoundError(f"no checkpoint found in {c.log_dir}")
         self.print("========", "recommend", "========")
@@ -767,7 +779,8 @@ class Trainer:
                 lists = _read_seen(c.recommend_shortlist_files[fi], b.B, cands.B)
                 kw = dict(shortlist=K.seen_lists(lists[self.rank::self.world], cands.B, self.device))
                 tail = " shortlist %d" % sum(len(s) for s in lists)
-            idx, score = self.model.recommend(mine, index, top, **kw)
+            dkw = {} if diversity is None else dict(diversity=diversity, pool=pool)
+            idx, score = self.model.recommend(mine, index, top, **kw, **dkw)
             part = (idx.cpu().numpy(), score.cpu().numpy())
             if c.recommend_target_files:
                 targets = _read_targets(c.recommend_target_files[fi], b.B, cands.B)
