@@ -17,7 +17,7 @@
 // diversify_kernel<J>: one wave (a 64-thread workgroup) per context, T = ceil(M / 16) tiles of 16 positions.
 // Gather: lane l keeps the candidate, score and inv of positions l and l + 64.  For tile t lane (r, h) fetches the
 // candidate of position 16 t + r from its lane and loads 16 bytes per column group of that row straight from C,
-// fm_topk.hip's operand layout -- which serves as the A and as the B operand of v_mfma_f32_16x16x4_f32 alike.
+// load_operands' layout (fm_rank_common.h) -- which serves as the A and as the B operand of v_mfma_f32_16x16x4_f32 alike.
 // Gram: row tile I's operands stay in registers while J runs over I .. T-1 (the diagonal tile multiplies I's
 // operands with themselves: no load); widths up to Kp = 128 gather tile J + 1 under tile J's products.  An
 // accumulator of lane (r, h) holds dot of positions 16 I + 4 h + i and 16 J + r; scaled, it goes to the fp32
@@ -30,9 +30,8 @@
 // Not tried: padding G's rows against the 4-way bank conflict of the tile stores; n matrix-vector passes in place
 // of the Gram for pools much larger than n; several contexts per workgroup.
 //
-// (Included by module.hip after fm_shortlist.hip.)  No atomics, no host read, no workspace; graph-capturable and
-// bitwise repeatable.
-#include "fm_common.h"
+// No atomics, no host read, no workspace; graph-capturable and bitwise repeatable.
+#include "fm_rank_common.h"
 
 namespace fm {
 
@@ -118,12 +117,7 @@ __global__ __launch_bounds__(kWave) void diversify_kernel(DiversifyArgs a) {
   // operands of tile t: lane (r, h) loads columns 16 g + 4 h .. + 3 of position 16 t + r's row (none: zeros)
   const auto gather = [&](int t, f32x4 (&v)[J]) {
     const int ct = cand_of(t, r);
-    const float* cp = a.C + (long long)(ct < 0 ? 0 : ct) * a.c_stride + 4 * h;
-#pragma unroll
-    for (int g = 0; g < J; ++g) {
-      v[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (ct >= 0 && topk::col(g, 0, h) < a.Kp) v[g] = *reinterpret_cast<const f32x4*>(cp + topk::kGroup * g);
-    }
+    load_operands<J>(a.C + (long long)(ct < 0 ? 0 : ct) * a.c_stride + 4 * h, h, a.Kp, v, ct >= 0);
   };
 
   for (int I = 0; I < T; ++I) {
@@ -233,27 +227,18 @@ inline size_t diversify_lds_bytes(int M) {
 
 // idx / score / mmr [nq, n]: n greedy picks from every context's pool.  -1: bad arguments; -3: launch error.
 inline int launch_diversify(const DiversifyArgs& a, hipStream_t stream) {
-  if (a.Kp < 4 || a.Kp > topk::kMaxKp || a.Kp % 4 || a.nq < 0 || a.nq >= (1ll << 31) || a.nc < 0 ||
-      a.nc >= (1ll << 31) || a.M < 1 || a.M > topk::kMaxK || a.n < 1 || a.n > a.M || !(a.lam >= 0.f && a.lam <= 1.f) ||
-      a.c_stride < a.Kp || a.c_stride % 4)
+  if (!profile_sizes_ok(a.nq, a.nc, a.Kp) || a.M < 1 || a.M > topk::kMaxK || a.n < 1 || a.n > a.M ||
+      !(a.lam >= 0.f && a.lam <= 1.f) || a.c_stride < a.Kp || a.c_stride % 4)
     return -1;
   if (a.nq == 0) return 0;
   if ((a.nc > 0 && (!a.C || !a.inv)) || !a.pool_idx || !a.pool_score || !a.idx || !a.score || !a.mmr ||
       (reinterpret_cast<uintptr_t>(a.C) & 15))
     return -1;
   const size_t lds = diversify_lds_bytes(a.M);
-#define FM_DIVERSIFY_CASE(JJ)                                                                             \
-  case JJ:                                                                                                \
-    hipLaunchKernelGGL((diversify_kernel<JJ>), dim3((unsigned)a.nq), dim3(kWave), lds, stream, a);        \
-    break;
-  switch (topk::groups(a.Kp)) {
-    FM_DIVERSIFY_CASE(1) FM_DIVERSIFY_CASE(2) FM_DIVERSIFY_CASE(3) FM_DIVERSIFY_CASE(4) FM_DIVERSIFY_CASE(5)
-    FM_DIVERSIFY_CASE(6) FM_DIVERSIFY_CASE(7) FM_DIVERSIFY_CASE(8) FM_DIVERSIFY_CASE(9) FM_DIVERSIFY_CASE(10)
-    FM_DIVERSIFY_CASE(11) FM_DIVERSIFY_CASE(12) FM_DIVERSIFY_CASE(13) FM_DIVERSIFY_CASE(14) FM_DIVERSIFY_CASE(15)
-    FM_DIVERSIFY_CASE(16)
-    default: return -1;
-  }
-#undef FM_DIVERSIFY_CASE
+  if (dispatch_groups(a.Kp, [&](auto j) {
+        hipLaunchKernelGGL((diversify_kernel<decltype(j)::value>), dim3((unsigned)a.nq), dim3(kWave), lds, stream, a);
+      }))
+    return -1;
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 

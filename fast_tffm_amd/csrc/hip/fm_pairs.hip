@@ -26,7 +26,7 @@
 // end, and the keys decode to (j, l, p): the sign of p travels in the key.  The [n, n] matrix never reaches
 // memory; no host read, no cross-wave wait, every loop bounded by n <= pairs::kMaxN.
 //
-// (Included after fm_topk.hip: f32x4 and topk_sort_rows are its.)
+// (Included after fm_topk.hip, which brings in fm_rank_common.h: f32x4 and topk_sort_rows are that header's.)
 #include "fm_common.h"
 #include "../pairs_key.h"
 

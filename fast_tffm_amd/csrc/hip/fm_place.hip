@@ -1,7 +1,7 @@
 // The place of a held-out candidate among all candidates, per query, from FM profiles (leave-one-out HR@k /
 // NDCG@k / MRR; the reference only scores examples).
 //
-//   s(q, c) = ((qb[q] + cb[c]) + dot(q, c)) + 0.f      fm_topk.hip's score, bit for bit (../topk_order.h: pi)
+//   s(q, c) = ((qb[q] + cb[c]) + dot(q, c)) + 0.f      fm_topk.hip's score, bit for bit (fm_rank_common.h)
 //   s_t = s(q, target[q]);  greater[q] = #{c : s(q, c) > s_t},  equal[q] = #{c : s(q, c) == s_t}  (>= 1: the target)
 //
 // and target[q] outside [0, nc) makes q unranked: all zeros.  The target holds the places greater + 1 .. greater +
@@ -9,12 +9,12 @@
 // exact fp32 scores: no atomics, no host read, bitwise repeatable, and independent of the slab plan.  The
 // [nq, nc] score matrix never reaches memory.
 //
-// 1. place_target_kernel: a thread per query runs the plain fmaf chain in pi's order -- the chain
-//    v_mfma_f32_16x16x4_f32 is (fm_topk.hip) -- and leaves s_t and a ranked flag in the workspace.
+// 1. place_target_kernel: a thread per query runs score_chain, the plain fmaf chain in pi's order -- the chain
+//    v_mfma_f32_16x16x4_f32 is -- and leaves s_t and a ranked flag in the workspace.
 // 2. place_count_kernel: the hot path, one workgroup of 4 waves per (64-query block, slab).  Wave w keeps the A
-//    operands of query tile 4 block + w in registers (fm_topk's layout: lane (r, h) holds columns 16 g + 4 h .. + 3
-//    of row r).  The candidates go through LDS once per workgroup instead of once per wave: a chunk of NT
-//    16-candidate tiles is staged as NT J items of 64 x 16 bytes, item (T, g) being exactly what the 64 lanes of a
+//    operands of query tile 4 block + w in registers (load_operands' layout: lane (r, h) holds columns
+//    16 g + 4 h .. + 3 of row r).  The candidates go through LDS once per workgroup instead of once per wave: a chunk
+//    of NT 16-candidate tiles is staged as NT J items of 64 x 16 bytes, item (T, g) being exactly what the 64 lanes of a
 //    wave feed to the matrix instructions 4 g .. 4 g + 3 of tile T, in lane order -- the waves split the items,
 //    each a coalesced-per-row 16-byte global load and a contiguous, conflict-free 1 KB LDS write, and every wave
 //    then reads its B operands back with contiguous 16-byte LDS reads.  Two buffers: the next chunk's global
@@ -25,39 +25,17 @@
 //    equal) to part[q][slab].  A wave whose tile lies past nq stages and keeps the barriers, and multiplies nothing.
 // 3. place_sum_kernel adds a query's parts into counts[nq, 2]; place_metric_kernel sums the metric terms of 1024
 //    contexts per workgroup in fp64 in context order, place_final_kernel the tiles in tile order, into the record.
+//    fm_shortlist.hip and fm_place_multi.hip run these passes on their own parts and terms.
 //
-// (Included by module.hip after fm_topk.hip -- f32x4 -- and rank_metrics.hip -- the discount table and its upload.
-// Every kernel here is compiled without the packed fp32 instructions.)
-#include "fm_common.h"
-#include "../place_order.h"
+// (Included by module.hip after rank_metrics.hip -- the discount table and its upload.  Every score kernel here is
+// compiled without the packed fp32 instructions.)
+#include "fm_rank_common.h"
 
 namespace fm {
 
-#if defined(__HIP_DEVICE_COMPILE__)
-#define FM_PLACE_FN __attribute__((target("no-packed-fp32-ops")))
-#else
-#define FM_PLACE_FN
-#endif
-// A function compiled for other target features than its caller's is called, not inlined -- the HIP header's
-// wrappers included -- so the two fp32 kernels use the compiler's builtins directly.
-#define FM_PLACE_BARRIER()                              \
-  do {                                                  \
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup"); \
-    __builtin_amdgcn_s_barrier();                       \
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); \
-  } while (0)
-
 __device__ double g_rank_harm[kRankMaxCutoff + 1];  // H (rank_table.h), uploaded once per device
 
-constexpr int kPlaceThreads = place::kWaves * kWave;
-
-struct PlaceArgs {
-  long long nq, nc;
-  int Kp;
-  const float* Q; long long q_stride;   // [nq, Kp], row stride in elements (16-byte aligned rows)
-  const float* C; long long c_stride;   // [nc, Kp]
-  const float* qb;                      // [nq]
-  const float* cb;                      // [nc]
+struct PlaceArgs : ProfileArgs {
   const int* target;                    // [nq]
   long long slab; int parts;            // place::plan
   float* st;                            // [nq] s_t (workspace)
@@ -66,13 +44,14 @@ struct PlaceArgs {
   int* counts;                          // [nq, 2]
 };
 
-struct PlaceMetricArgs {
+// A reduce pass over n contexts: NI integer words, then 3 nk fp64 words (place::rec_words, place::multi_rec_words).
+struct MetricArgs {
   long long n;
-  const int* counts;   // [n, 2]
+  const int* counts;   // [n, 2], or [nnz, 2] under MultiMetricArgs
   int nk, k[kRankMaxCutoffs];
   long long ntiles;
-  unsigned long long* tiles;  // [ntiles][2 + 3 nk] (unused when ntiles == 1)
-  unsigned long long* rec;    // [2 + 3 nk]
+  unsigned long long* tiles;  // [ntiles][NI + 3 nk] (unused when ntiles == 1)
+  unsigned long long* rec;    // [NI + 3 nk]
 };
 
 __global__ FM_PLACE_FN __launch_bounds__(kPlaceThreads) void place_target_kernel(PlaceArgs a) {
@@ -81,20 +60,8 @@ __global__ FM_PLACE_FN __launch_bounds__(kPlaceThreads) void place_target_kernel
   const int t = a.target[q];
   const bool ranked = t >= 0 && t < a.nc;
   float s = 0.f;
-  if (ranked) {
-    const float* qr = a.Q + q * a.q_stride;
-    const float* cr = a.C + (long long)t * a.c_stride;
-    float dot = 0.f;
-    const int G = (a.Kp + topk::kGroup - 1) / topk::kGroup;
-    for (int g = 0; g < G; ++g)
-      for (int e = 0; e < 4; ++e)
-        for (int h = 0; h < 4; ++h)
-          if (topk::kGroup * g + 4 * h < a.Kp) {
-            const int c = topk::kGroup * g + 4 * h + e;
-            dot = __builtin_fmaf(qr[c], cr[c], dot);
-          }
-    s = ((a.qb[q] + a.cb[t]) + dot) + 0.f;
-  }
+  if (ranked)
+    s = score_of(a.qb[q], a.cb[t], score_chain(a.Q + q * a.q_stride, a.C + (long long)t * a.c_stride, a.Kp));
   a.st[q] = s;
   a.flag[q] = ranked ? 1 : 0;
 }
@@ -123,16 +90,14 @@ __global__ FM_PLACE_FN __launch_bounds__(kPlaceThreads) void place_count_kernel(
   const long long c_begin = (long long)part * a.slab;
   const long long c_end = c_begin + a.slab < a.nc ? c_begin + a.slab : a.nc;   // > c_begin: part < parts
 
-  // A operands: query row q0 + r, columns 16 g + 4 h .. + 3 (zeros past Kp)
+  // A operands: query row q0 + r (load_operands; an idle wave's stay zero -- a wave-uniform branch, not a per-lane
+  // condition on every load)
   f32x4 qa[J];
 #pragma unroll
   for (int g = 0; g < J; ++g) qa[g] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (active) {
     const long long qr = q0 + r < a.nq ? q0 + r : a.nq - 1;
-    const float* qp = a.Q + qr * a.q_stride + 4 * h;
-#pragma unroll
-    for (int g = 0; g < J; ++g)
-      if (topk::kGroup * g + 4 * h < a.Kp) qa[g] = *reinterpret_cast<const f32x4*>(qp + topk::kGroup * g);
+    load_operands<J>(a.Q + qr * a.q_stride + 4 * h, h, a.Kp, qa);
   }
   // this lane's 4 result rows: queries q0 + 4 h + i
   float qbv[4], stv[4];
@@ -159,8 +124,7 @@ __global__ FM_PLACE_FN __launch_bounds__(kPlaceThreads) void place_count_kernel(
         const int T = it / J, g = it - T * J;
         const long long c = c0 + T * topk::kTile + r;
         const long long lc = c < c_end ? c : c_end - 1;
-        if (topk::kGroup * g + 4 * h < a.Kp)
-          stg[s] = *reinterpret_cast<const f32x4*>(a.C + lc * a.c_stride + topk::kGroup * g + 4 * h);
+        stg[s] = load_fragment(a.C + lc * a.c_stride + 4 * h, g, h, a.Kp);
       }
     }
     if (tid < CH) {
@@ -234,15 +198,17 @@ __global__ FM_PLACE_FN __launch_bounds__(kPlaceThreads) void place_count_kernel(
   }
 }
 
-// counts[q] = the sum of q's parts; L lanes (a power of two <= 64) per query
-__global__ __launch_bounds__(kPlaceThreads) void place_sum_kernel(PlaceArgs a, int L) {
+// counts[i] = the sum of row i's parts, of n rows (queries, or entries of fm_place_multi.hip); L lanes (a power of
+// two <= 64) per row
+__global__ __launch_bounds__(kPlaceThreads) void place_sum_kernel(const int* part, int* counts, long long n, int parts,
+                                                                  int L) {
   const long long t = (long long)blockIdx.x * kPlaceThreads + threadIdx.x;
   const long long q = t / L;
   const int sub = (int)(t - q * L);
   int gt = 0, eq = 0;
-  if (q < a.nq) {
-    const int* p = a.part + q * a.parts * 2;
-    for (int j = sub; j < a.parts; j += L) {
+  if (q < n) {
+    const int* p = part + q * parts * 2;
+    for (int j = sub; j < parts; j += L) {
       gt += p[2 * j];
       eq += p[2 * j + 1];
     }
@@ -251,15 +217,17 @@ __global__ __launch_bounds__(kPlaceThreads) void place_sum_kernel(PlaceArgs a, i
     gt += __shfl_xor(gt, m);
     eq += __shfl_xor(eq, m);
   }
-  if (sub == 0 && q < a.nq) {
-    a.counts[2 * q] = gt;
-    a.counts[2 * q + 1] = eq;
+  if (sub == 0 && q < n) {
+    counts[2 * q] = gt;
+    counts[2 * q + 1] = eq;
   }
 }
 
 // The record words of one tile of 1024 contexts: thread c < 3 nk owns fp64 channel c, threads 32 / 33 the two
-// integer words; each adds its channel's terms in context order.
-__global__ __launch_bounds__(kPlaceThreads) void place_metric_kernel(PlaceMetricArgs m) {
+// integer words; each adds its channel's terms in context order.  (multi_metric_kernel of fm_place_multi.hip is the
+// same reduce with other terms and three integer words; written as one function over a terms callback, both kept
+// their term arrays in scratch memory, so they stay apart.)
+__global__ __launch_bounds__(kPlaceThreads) void place_metric_kernel(MetricArgs m) {
   __shared__ double sd[kPlaceThreads][3 * kRankMaxCutoffs];
   __shared__ long long si[kPlaceThreads][2];
   const int tid = threadIdx.x;
@@ -294,11 +262,12 @@ __global__ __launch_bounds__(kPlaceThreads) void place_metric_kernel(PlaceMetric
   if (tid == 32 || tid == 33) out[tid - 32] = (unsigned long long)iacc;
 }
 
-__global__ __launch_bounds__(kWave) void place_final_kernel(PlaceMetricArgs m) {
+// The tiles' partial records added in tile order: ni integer words, then the fp64 words.
+__global__ __launch_bounds__(kWave) void place_final_kernel(MetricArgs m, int ni) {
   const int tid = threadIdx.x;
-  const int words = place::rec_words(m.nk);
+  const int words = ni + 3 * m.nk;
   if (tid >= words) return;
-  if (tid < 2) {
+  if (tid < ni) {
     long long s = 0;
     for (long long t = 0; t < m.ntiles; ++t) s += (long long)m.tiles[t * words + tid];
     m.rec[tid] = (unsigned long long)s;
@@ -313,16 +282,30 @@ __global__ __launch_bounds__(kWave) void place_final_kernel(PlaceMetricArgs m) {
 inline long long place_tiles(long long n) { return (n + place::kMetricTile - 1) / place::kMetricTile; }
 inline long long place_pad8(long long b) { return (b + 7) / 8 * 8; }
 
-// Bytes of place_metrics' scratch (the tiles' partial records; none for up to 1024 contexts).
-inline long long place_metrics_workspace_bytes(long long n, int nk) {
+// Bytes of a reduce pass's scratch (the tiles' partial records of `words` words; none for up to 1024 contexts).
+inline long long metric_workspace_bytes(long long n, int words) {
   const long long t = place_tiles(n);
-  return t > 1 ? t * place::rec_words(nk) * 8 : 0;
+  return t > 1 ? t * words * 8 : 0;
+}
+inline long long place_metrics_workspace_bytes(long long n, int nk) {
+  return metric_workspace_bytes(n, place::rec_words(nk));
 }
 
-// Workspace bytes of a launch_place call: [tiles][s_t][flag][parts].
+// The layout [tiles][s_t][flag][parts] of a call with `parts` partial counts per query: its bytes, and its arrays
+// into `a` (ws 8-byte aligned).
+inline long long place_layout_bytes(long long nq, int parts, int nk) {
+  return place_metrics_workspace_bytes(nq, nk) + place_pad8(nq * 4) * 2 + nq * parts * 8;
+}
+inline void place_carve(PlaceArgs& a, void* ws, int nk) {
+  char* base = static_cast<char*>(ws) + place_metrics_workspace_bytes(a.nq, nk);
+  a.st = reinterpret_cast<float*>(base);
+  a.flag = reinterpret_cast<int*>(base + place_pad8(a.nq * 4));
+  a.part = reinterpret_cast<int*>(base + 2 * place_pad8(a.nq * 4));
+}
+
+// Workspace bytes of a launch_place call.
 inline long long place_workspace_bytes(long long nq, long long nc, int nk) {
-  const place::Plan p = place::plan(nq, nc);
-  return place_metrics_workspace_bytes(nq, nk) + place_pad8(nq * 4) * 2 + nq * p.parts * 8;
+  return place_layout_bytes(nq, place::plan(nq, nc).parts, nk);
 }
 
 // D and H on the current device: uploaded by the first call there (a synchronous copy: not inside a capture).
@@ -344,38 +327,56 @@ static int place_tables_ready() {
   return 0;
 }
 
-// The record of n >= 1 (greater, equal) rows (equal <= 0: unranked) at the nk cutoffs k, asynchronously on st.
+// A reduce pass on st: `m` holds what the tile kernel reads beyond the common fields, which are filled in here.
 // 0 or a hip error code; -1: bad arguments; -2: workspace too small; -7: bad cutoffs.
-inline int launch_place_metrics(const int* counts, long long n, const int* k, int nk, void* rec, void* ws,
-                                size_t ws_bytes, hipStream_t st) {
-  if (!counts || !rec || n < 1 || n >= (1ll << 31) || (reinterpret_cast<uintptr_t>(rec) & 7) ||
+template <int NI, typename M>
+inline int launch_metric_pass(void (*tile_kernel)(M), M m, const int* counts, long long n, const int* k, int nk,
+                              void* rec, void* ws, size_t ws_bytes, hipStream_t st) {
+  if (!rec || n < 1 || n >= (1ll << 31) || (reinterpret_cast<uintptr_t>(rec) & 7) ||
       (reinterpret_cast<uintptr_t>(ws) & 7))
     return -1;
   if (!rank_cutoffs_ok(k, nk)) return -7;
-  if ((long long)ws_bytes < place_metrics_workspace_bytes(n, nk) || (!ws && place_tiles(n) > 1)) return -2;
+  if ((long long)ws_bytes < metric_workspace_bytes(n, NI + 3 * nk) || (!ws && place_tiles(n) > 1)) return -2;
   if (const int rc = place_tables_ready()) return rc;
-  PlaceMetricArgs m{};
   m.n = n; m.counts = counts; m.nk = nk;
   for (int i = 0; i < nk; ++i) m.k[i] = k[i];
   m.ntiles = place_tiles(n);
   m.tiles = static_cast<unsigned long long*>(ws);
   m.rec = static_cast<unsigned long long*>(rec);
-  hipLaunchKernelGGL(place_metric_kernel, dim3((unsigned)m.ntiles), dim3(kPlaceThreads), 0, st, m);
-  if (m.ntiles > 1) hipLaunchKernelGGL(place_final_kernel, dim3(1), dim3(kWave), 0, st, m);
+  hipLaunchKernelGGL(tile_kernel, dim3((unsigned)m.ntiles), dim3(kPlaceThreads), 0, st, m);
+  if (m.ntiles > 1)
+    hipLaunchKernelGGL(place_final_kernel, dim3(1), dim3(kWave), 0, st, static_cast<const MetricArgs&>(m), NI);
   return hipGetLastError() == hipSuccess ? 0 : -3;
+}
+
+// The record of n >= 1 (greater, equal) rows (equal <= 0: unranked) at the nk cutoffs k, asynchronously on st.
+inline int launch_place_metrics(const int* counts, long long n, const int* k, int nk, void* rec, void* ws,
+                                size_t ws_bytes, hipStream_t st) {
+  if (!counts) return -1;
+  return launch_metric_pass<2>(place_metric_kernel, MetricArgs{}, counts, n, k, nk, rec, ws, ws_bytes, st);
+}
+
+// counts[i] = the sum of row i's `parts` partial counts, of n rows.
+inline void launch_place_sum(const int* part, int* counts, long long n, int parts, hipStream_t st) {
+  int L = 1;
+  while (L < kWave && L < parts) L <<= 1;
+  hipLaunchKernelGGL(place_sum_kernel, dim3((unsigned)((n * L + kPlaceThreads - 1) / kPlaceThreads)),
+                     dim3(kPlaceThreads), 0, st, part, counts, n, parts, L);
+}
+
+// What launch_place and fm_shortlist.hip's launch_place_shortlist ask of their common arguments.
+inline bool place_args_ok(const PlaceArgs& a, const void* ws) {
+  return profile_rows_ok(a) && a.target && a.counts && ws && !(reinterpret_cast<uintptr_t>(ws) & 7);
 }
 
 // fm_seen.hip: takes every query's seen candidates (its target apart) out of counts again.
 inline int launch_place_seen(const PlaceArgs& a, const SeenArgs& sn, hipStream_t st);
 
 // counts[nq, 2] and the record of nq >= 1 queries against nc >= 1 candidates; `sn`: the lists of candidates that do
-// not compete (null: none, and nothing more is launched).  Codes as launch_place_metrics.
+// not compete (null: none, and nothing more is launched).  Codes as launch_metric_pass.
 inline int launch_place(PlaceArgs a, const int* k, int nk, void* rec, void* ws, size_t ws_bytes, hipStream_t st,
                         const SeenArgs* sn = nullptr) {
-  if (a.Kp < 4 || a.Kp > topk::kMaxKp || a.Kp % 4 || a.nq < 1 || a.nc < 1 || a.nc >= (1ll << 31) ||
-      a.nq >= (1ll << 31) || !a.Q || !a.C || !a.qb || !a.cb || !a.target || !a.counts || !ws ||
-      (reinterpret_cast<uintptr_t>(ws) & 7))
-    return -1;
+  if (!place_args_ok(a, ws)) return -1;
   if (!rank_cutoffs_ok(k, nk)) return -7;
   if ((long long)ws_bytes < place_workspace_bytes(a.nq, a.nc, nk)) return -2;
   const place::Plan p = place::plan(a.nq, a.nc);
@@ -384,32 +385,19 @@ inline int launch_place(PlaceArgs a, const int* k, int nk, void* rec, void* ws, 
   const long long qblocks = (a.nq + place::kQueryBlock - 1) / place::kQueryBlock;
   const long long blocks = qblocks * a.parts;
   if (blocks >= (1ll << 31)) return -1;
-  char* base = static_cast<char*>(ws);
-  const long long mbytes = place_metrics_workspace_bytes(a.nq, nk);
-  a.st = reinterpret_cast<float*>(base + mbytes);
-  a.flag = reinterpret_cast<int*>(base + mbytes + place_pad8(a.nq * 4));
-  a.part = reinterpret_cast<int*>(base + mbytes + 2 * place_pad8(a.nq * 4));
+  place_carve(a, ws, nk);
   const unsigned qgrid = (unsigned)((a.nq + kPlaceThreads - 1) / kPlaceThreads);
   hipLaunchKernelGGL(place_target_kernel, dim3(qgrid), dim3(kPlaceThreads), 0, st, a);
-#define FM_PLACE_CASE(JJ)                                                                                      \
-  case JJ:                                                                                                     \
-    hipLaunchKernelGGL((place_count_kernel<JJ>), dim3((unsigned)blocks), dim3(kPlaceThreads), 0, st, a, qblocks); \
-    break;
-  switch (topk::groups(a.Kp)) {
-    FM_PLACE_CASE(1) FM_PLACE_CASE(2) FM_PLACE_CASE(3) FM_PLACE_CASE(4) FM_PLACE_CASE(5) FM_PLACE_CASE(6)
-    FM_PLACE_CASE(7) FM_PLACE_CASE(8) FM_PLACE_CASE(9) FM_PLACE_CASE(10) FM_PLACE_CASE(11) FM_PLACE_CASE(12)
-    FM_PLACE_CASE(13) FM_PLACE_CASE(14) FM_PLACE_CASE(15) FM_PLACE_CASE(16)
-    default: return -1;
-  }
-#undef FM_PLACE_CASE
-  int L = 1;
-  while (L < kWave && L < a.parts) L <<= 1;
-  const long long sum_threads = a.nq * L;
-  hipLaunchKernelGGL(place_sum_kernel, dim3((unsigned)((sum_threads + kPlaceThreads - 1) / kPlaceThreads)),
-                     dim3(kPlaceThreads), 0, st, a, L);
+  if (dispatch_groups(a.Kp, [&](auto j) {
+        hipLaunchKernelGGL((place_count_kernel<decltype(j)::value>), dim3((unsigned)blocks), dim3(kPlaceThreads), 0, st,
+                           a, qblocks);
+      }))
+    return -1;
+  launch_place_sum(a.part, a.counts, a.nq, a.parts, st);
   if (hipGetLastError() != hipSuccess) return -3;
   if (sn)
     if (const int rc = launch_place_seen(a, *sn, st)) return rc;
+  const long long mbytes = place_metrics_workspace_bytes(a.nq, nk);
   return launch_place_metrics(a.counts, a.nq, k, nk, rec, mbytes ? ws : nullptr, (size_t)mbytes, st);
 }
 

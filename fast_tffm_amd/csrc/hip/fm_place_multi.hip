@@ -14,7 +14,7 @@
 //    (metric_common.hip's block scan per tile of 256, then the tile totals) and write the row table (context, first
 //    entry, length); the grid of every later pass is sized from nq + nnz / S, the most rows there can be, and the
 //    surplus rows have length 0.
-// 2. multi_segment_kernel: 32 lanes per row.  A lane runs place_target_kernel's fmaf chain for its entry -- nothing
+// 2. multi_segment_kernel: 32 lanes per row.  A lane runs score_chain (fm_rank_common.h) for its entry -- nothing
 //    else is exact against the matrix instruction -- leaves s(q, t) and the entry's context, and the segment is
 //    sorted descending in LDS by rank counting (equal scores in entry order), carrying the entry's position.
 // 3. multi_count_kernel: place_count_kernel's skeleton -- one workgroup of 4 waves per (64-row block, slab), a
@@ -30,17 +30,18 @@
 //    histogram into its prefix sums and (greater, equal) of every entry goes to part[entry][slab].
 // 4. place_sum_kernel (fm_place.hip) adds an entry's parts into counts[nnz, 2], in entry order.
 // 5. multi_seen_kernel: place_seen_kernel's method per entry -- 16 lanes stride over the context's seen list, skip
-//    the members of T_q (a binary search of the ascending targets), score the rest with the fmaf chain, and the
+//    the members of T_q (a binary search of the ascending targets), score the rest with score_chain, and the
 //    group's first lane subtracts the sums from counts[entry].
 // 6. multi_metric_kernel: a thread per context walks its entries (place::multi_terms: fp64 in ascending target
-//    order); 1024 contexts per workgroup in context order, multi_final_kernel the tiles in tile order, as
-//    place_metric_kernel does.  A context with thousands of targets is walked by one thread: correct, but slow.
+//    order); 1024 contexts per workgroup in context order, place_final_kernel (fm_place.hip) the tiles in tile
+//    order, as place_metric_kernel does.  A context with thousands of targets is walked by one thread: correct, but
+//    slow.
 //
 // A malformed list gives unspecified counts but no access out of bounds: windows are clamped to [0, nnz], targets
 // into [0, nc), and no row index past the table is written.
-// (Included by module.hip after fm_seen.hip.  The score kernels are compiled without the packed fp32 instructions.)
-#include "fm_common.h"
-#include "../place_order.h"
+// (Included by module.hip after fm_place.hip, whose sum and metric passes it launches.  The score kernels are compiled
+// without the packed fp32 instructions.)
+#include "fm_rank_common.h"
 
 namespace fm {
 
@@ -48,13 +49,8 @@ constexpr int kMultiScanTile = kBlock;    // contexts per tile of the row scan
 constexpr int kMultiSegRows = kBlock / place::kSegment;   // rows per workgroup of multi_segment_kernel
 static_assert(place::kSegment == 32, "multi_segment_kernel: one entry per lane of half a wave");
 
-struct MultiArgs {
-  long long nq, nc, nnz;
-  int Kp;
-  const float* Q; long long q_stride;
-  const float* C; long long c_stride;
-  const float* qb;
-  const float* cb;
+struct MultiArgs : ProfileArgs {
+  long long nnz;
   const int* off;       // [nq + 1]
   const int* idx;       // [nnz]
   long long rows_max;   // place::multi_rows_max(nq, nnz)
@@ -73,22 +69,10 @@ struct MultiArgs {
   int* counts;          // [nnz, 2]
 };
 
-struct MultiMetricArgs {
-  long long n, nnz;
-  const int* counts;   // [nnz, 2]
+struct MultiMetricArgs : MetricArgs {   // counts [nnz, 2]; the record: place::multi_rec_words
+  long long nnz;
   const int* off;      // [n + 1]
-  int nk, k[kRankMaxCutoffs];
-  long long ntiles;
-  unsigned long long* tiles;  // [ntiles][3 + 3 nk] (unused when ntiles == 1)
-  unsigned long long* rec;    // [3 + 3 nk]
 };
-
-// context q's window [b0, e0) of the entries, clamped into [0, nnz]
-__device__ inline void multi_window(const int* off, long long nnz, long long q, int& b0, int& e0) {
-  const int o0 = off[q], o1 = off[q + 1];
-  b0 = o0 < 0 ? 0 : o0 > nnz ? (int)nnz : o0;
-  e0 = o1 < b0 ? b0 : o1 > nnz ? (int)nnz : o1;
-}
 
 __global__ __launch_bounds__(kBlock) void multi_rows_tile_kernel(MultiArgs a) {
   __shared__ int sh[kWavesPerBlock];
@@ -96,7 +80,7 @@ __global__ __launch_bounds__(kBlock) void multi_rows_tile_kernel(MultiArgs a) {
   int n = 0;
   if (q < a.nq) {
     int b0, e0;
-    multi_window(a.off, a.nnz, q, b0, e0);
+    csr_window(a.off, a.nnz, q, b0, e0);
     n = (int)place::segments(e0 - b0);
   }
   int excl, total;
@@ -123,7 +107,7 @@ __global__ __launch_bounds__(kBlock) void multi_rows_fill_kernel(MultiArgs a, lo
   const long long i = (long long)blockIdx.x * kBlock + threadIdx.x;
   if (i < a.nq) {
     int b0, e0;
-    multi_window(a.off, a.nnz, i, b0, e0);
+    csr_window(a.off, a.nnz, i, b0, e0);
     const long long base = (long long)a.tiletot[i / kMultiScanTile] + a.rowstart[i];
     for (long long seg = 0; b0 + seg * place::kSegment < e0; ++seg) {
       const long long r = base + seg;
@@ -150,18 +134,7 @@ __global__ FM_PLACE_FN __launch_bounds__(kBlock) void multi_segment_kernel(Multi
     const long long e = (long long)a.rowbeg[row] + j;
     int t = a.idx[e];
     t = t < 0 ? 0 : t >= a.nc ? (int)(a.nc - 1) : t;
-    const float* qr = a.Q + q * a.q_stride;
-    const float* cr = a.C + (long long)t * a.c_stride;
-    float dot = 0.f;
-    const int G = (a.Kp + topk::kGroup - 1) / topk::kGroup;
-    for (int g = 0; g < G; ++g)
-      for (int e4 = 0; e4 < 4; ++e4)
-        for (int h = 0; h < 4; ++h)
-          if (topk::kGroup * g + 4 * h < a.Kp) {
-            const int c = topk::kGroup * g + 4 * h + e4;
-            dot = __builtin_fmaf(qr[c], cr[c], dot);
-          }
-    s = ((a.qb[q] + a.cb[t]) + dot) + 0.f;
+    s = score_of(a.qb[q], a.cb[t], score_chain(a.Q + q * a.q_stride, a.C + (long long)t * a.c_stride, a.Kp));
     a.est[e] = s;
     a.entq[e] = (int)q;
   }
@@ -218,16 +191,13 @@ __global__ FM_PLACE_FN __launch_bounds__(kPlaceThreads) void multi_count_kernel(
   }
   for (int i = tid; i < RB * HB; i += kPlaceThreads) sH[i] = 0;
 
-  // A operands: the context of row r0 + r, columns 16 g + 4 h .. + 3 (zeros past Kp)
+  // A operands: the context of row r0 + r (load_operands; an idle wave's stay zero, as in place_count_kernel)
   f32x4 qa[J];
 #pragma unroll
   for (int g = 0; g < J; ++g) qa[g] = f32x4{0.f, 0.f, 0.f, 0.f};
   if (active) {
     const long long qr = r0 + r < nrows ? a.rowq[r0 + r] : a.rowq[nrows - 1];
-    const float* qp = a.Q + qr * a.q_stride + 4 * h;
-#pragma unroll
-    for (int g = 0; g < J; ++g)
-      if (topk::kGroup * g + 4 * h < a.Kp) qa[g] = *reinterpret_cast<const f32x4*>(qp + topk::kGroup * g);
+    load_operands<J>(a.Q + qr * a.q_stride + 4 * h, h, a.Kp, qa);
   }
   // this lane's 4 result rows r0 + 4 h + i: the context's base score and the row's smallest threshold
   float qbv[4], mn[4];
@@ -252,8 +222,7 @@ __global__ FM_PLACE_FN __launch_bounds__(kPlaceThreads) void multi_count_kernel(
         const int T = it / J, g = it - T * J;
         const long long c = c0 + T * topk::kTile + r;
         const long long lc = c < c_end ? c : c_end - 1;
-        if (topk::kGroup * g + 4 * h < a.Kp)
-          stg[s] = *reinterpret_cast<const f32x4*>(a.C + lc * a.c_stride + topk::kGroup * g + 4 * h);
+        stg[s] = load_fragment(a.C + lc * a.c_stride + 4 * h, g, h, a.Kp);
       }
     }
     if (tid < CH) {
@@ -389,39 +358,15 @@ __global__ FM_PLACE_FN __launch_bounds__(kPlaceThreads) void multi_seen_kernel(M
     const int qe = a.entq[e];
     const long long q = qe < 0 ? 0 : qe >= a.nq ? a.nq - 1 : qe;   // (in range unless the lists are malformed)
     int b0, e0, t0, t1;
-    multi_window(sn.off, sn.nnz, q, b0, e0);
-    multi_window(a.off, a.nnz, q, t0, t1);
+    csr_window(sn.off, sn.nnz, q, b0, e0);
+    csr_window(a.off, a.nnz, q, t0, t1);
     const float ste = a.est[e], qbq = a.qb[q];
     const float* qr = a.Q + q * a.q_stride;
-    const int G = (a.Kp + topk::kGroup - 1) / topk::kGroup;
     for (int p = b0 + sub; p < e0; p += kMultiSeenLanes) {
       const int c = sn.idx[p];
       if (c < 0 || c >= a.nc) continue;
-      int lo = t0, hi = t1;   // is c one of the context's targets?  (they always compete)
-      while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (a.idx[mid] < c) lo = mid + 1;
-        else hi = mid;
-      }
-      if (lo < t1 && a.idx[lo] == c) continue;
-      const float* cr = a.C + (long long)c * a.c_stride;
-      float dot = 0.f;
-      for (int g = 0; g < G; ++g) {
-        f32x4 qf[4], cf[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-          qf[h] = cf[h] = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (topk::kGroup * g + 4 * h < a.Kp) {
-            qf[h] = *reinterpret_cast<const f32x4*>(qr + topk::kGroup * g + 4 * h);
-            cf[h] = *reinterpret_cast<const f32x4*>(cr + topk::kGroup * g + 4 * h);
-          }
-        }
-#pragma unroll
-        for (int e4 = 0; e4 < 4; ++e4)
-#pragma unroll
-          for (int h = 0; h < 4; ++h) dot = __builtin_fmaf(qf[h][e4], cf[h][e4], dot);
-      }
-      const float s = ((qbq + a.cb[c]) + dot) + 0.f;
+      if (seen_contains(a.idx, t0, t1, c)) continue;   // one of the context's targets: they always compete
+      const float s = score_of(qbq, a.cb[c], score_chain(qr, a.C + (long long)c * a.c_stride, a.Kp));
       gt += (int)(s > ste);
       eq += (int)(s == ste);
     }
@@ -439,7 +384,7 @@ __global__ FM_PLACE_FN __launch_bounds__(kPlaceThreads) void multi_seen_kernel(M
 }
 
 // The record words of one tile of 1024 contexts: thread c < 3 nk owns fp64 channel c, threads 32 .. 34 the three
-// integer words; each adds its channel's terms in context order.
+// integer words; each adds its channel's terms in context order (place_metric_kernel's reduce).
 __global__ __launch_bounds__(kPlaceThreads) void multi_metric_kernel(MultiMetricArgs m) {
   __shared__ double sd[kPlaceThreads][3 * kRankMaxCutoffs];
   __shared__ long long si[kPlaceThreads][3];
@@ -454,7 +399,7 @@ __global__ __launch_bounds__(kPlaceThreads) void multi_metric_kernel(MultiMetric
     long long ranked = 0, entries = 0, ab = 0;
     if (q < m.n) {
       int b0, e0;
-      multi_window(m.off, m.nnz, q, b0, e0);
+      csr_window(m.off, m.nnz, q, b0, e0);
       if (e0 > b0) {
         ranked = 1;
         entries = e0 - b0;
@@ -478,28 +423,12 @@ __global__ __launch_bounds__(kPlaceThreads) void multi_metric_kernel(MultiMetric
   if (tid >= 32 && tid < 35) out[tid - 32] = (unsigned long long)iacc;
 }
 
-__global__ __launch_bounds__(kWave) void multi_final_kernel(MultiMetricArgs m) {
-  const int tid = threadIdx.x;
-  const int words = place::multi_rec_words(m.nk);
-  if (tid >= words) return;
-  if (tid < 3) {
-    long long s = 0;
-    for (long long t = 0; t < m.ntiles; ++t) s += (long long)m.tiles[t * words + tid];
-    m.rec[tid] = (unsigned long long)s;
-  } else {
-    double s = 0.0;
-    for (long long t = 0; t < m.ntiles; ++t) s += __longlong_as_double((long long)m.tiles[t * words + tid]);
-    m.rec[tid] = (unsigned long long)__double_as_longlong(s);
-  }
-}
-
 // ---- host side ------------------------------------------------------------------------------------------------
 inline long long multi_scan_tiles(long long nq) { return (nq + kMultiScanTile - 1) / kMultiScanTile; }
 
 // Bytes of place_multi_metrics' scratch (the tiles' partial records; none for up to 1024 contexts).
 inline long long place_multi_metrics_workspace_bytes(long long n, int nk) {
-  const long long t = place_tiles(n);
-  return t > 1 ? t * place::multi_rec_words(nk) * 8 : 0;
+  return metric_workspace_bytes(n, place::multi_rec_words(nk));
 }
 
 // Workspace bytes of a launch_place_multi call:
@@ -513,34 +442,22 @@ inline long long place_multi_workspace_bytes(long long nq, long long nc, long lo
 }
 
 // The record of n >= 1 contexts from the (greater, equal) pairs of their entries (off [n + 1] over counts [nnz, 2]),
-// asynchronously on st.  Codes as launch_place_metrics.
+// asynchronously on st.  Codes as launch_metric_pass.
 inline int launch_place_multi_metrics(const int* counts, const int* off, long long n, long long nnz, const int* k,
                                       int nk, void* rec, void* ws, size_t ws_bytes, hipStream_t st) {
-  if (!off || !rec || n < 1 || n >= (1ll << 31) || nnz < 0 || nnz >= (1ll << 31) || (!counts && nnz) ||
-      (reinterpret_cast<uintptr_t>(rec) & 7) || (reinterpret_cast<uintptr_t>(ws) & 7))
-    return -1;
-  if (!rank_cutoffs_ok(k, nk)) return -7;
-  if ((long long)ws_bytes < place_multi_metrics_workspace_bytes(n, nk) || (!ws && place_tiles(n) > 1)) return -2;
-  if (const int rc = place_tables_ready()) return rc;
+  if (!off || nnz < 0 || nnz >= (1ll << 31) || (!counts && nnz)) return -1;
   MultiMetricArgs m{};
-  m.n = n; m.nnz = nnz; m.counts = counts; m.off = off; m.nk = nk;
-  for (int i = 0; i < nk; ++i) m.k[i] = k[i];
-  m.ntiles = place_tiles(n);
-  m.tiles = static_cast<unsigned long long*>(ws);
-  m.rec = static_cast<unsigned long long*>(rec);
-  hipLaunchKernelGGL(multi_metric_kernel, dim3((unsigned)m.ntiles), dim3(kPlaceThreads), 0, st, m);
-  if (m.ntiles > 1) hipLaunchKernelGGL(multi_final_kernel, dim3(1), dim3(kWave), 0, st, m);
-  return hipGetLastError() == hipSuccess ? 0 : -3;
+  m.nnz = nnz; m.off = off;
+  return launch_metric_pass<3>(multi_metric_kernel, m, counts, n, k, nk, rec, ws, ws_bytes, st);
 }
 
 // counts[nnz, 2] and the record of nq >= 1 contexts with nnz >= 0 targets together against nc >= 1 candidates;
-// `sn`: the lists of candidates that do not compete (null: none).  Codes as launch_place_metrics.
+// `sn`: the lists of candidates that do not compete (null: none).  Codes as launch_metric_pass.
 inline int launch_place_multi(MultiArgs a, const int* k, int nk, void* rec, void* ws, size_t ws_bytes,
                               hipStream_t st, const SeenArgs* sn = nullptr) {
   a.rows_max = place::multi_rows_max(a.nq, a.nnz);
-  if (a.Kp < 4 || a.Kp > topk::kMaxKp || a.Kp % 4 || a.nq < 1 || a.nc < 1 || a.nc >= (1ll << 31) ||
-      a.nq >= (1ll << 31) || a.nnz < 0 || a.rows_max >= (1ll << 31) || !a.Q || !a.C || !a.qb || !a.cb || !a.off ||
-      (a.nnz && (!a.idx || !a.counts)) || !ws || (reinterpret_cast<uintptr_t>(ws) & 7))
+  if (!profile_rows_ok(a) || a.nnz < 0 || a.rows_max >= (1ll << 31) || !a.off || (a.nnz && (!a.idx || !a.counts)) ||
+      !ws || (reinterpret_cast<uintptr_t>(ws) & 7))
     return -1;
   if (!rank_cutoffs_ok(k, nk)) return -7;
   if ((long long)ws_bytes < place_multi_workspace_bytes(a.nq, a.nc, a.nnz, nk)) return -2;
@@ -576,22 +493,12 @@ inline int launch_place_multi(MultiArgs a, const int* k, int nk, void* rec, void
     hipLaunchKernelGGL(multi_rows_fill_kernel, grid(a.nq > a.rows_max ? a.nq : a.rows_max), dim3(kBlock), 0, st, a,
                        stiles);
     hipLaunchKernelGGL(multi_segment_kernel, grid(a.rows_max * place::kSegment), dim3(kBlock), 0, st, a);
-#define FM_MULTI_CASE(JJ)                                                                                      \
-  case JJ:                                                                                                     \
-    hipLaunchKernelGGL((multi_count_kernel<JJ>), dim3((unsigned)blocks), dim3(kPlaceThreads), 0, st, a, rblocks); \
-    break;
-    switch (topk::groups(a.Kp)) {
-      FM_MULTI_CASE(1) FM_MULTI_CASE(2) FM_MULTI_CASE(3) FM_MULTI_CASE(4) FM_MULTI_CASE(5) FM_MULTI_CASE(6)
-      FM_MULTI_CASE(7) FM_MULTI_CASE(8) FM_MULTI_CASE(9) FM_MULTI_CASE(10) FM_MULTI_CASE(11) FM_MULTI_CASE(12)
-      FM_MULTI_CASE(13) FM_MULTI_CASE(14) FM_MULTI_CASE(15) FM_MULTI_CASE(16)
-      default: return -1;
-    }
-#undef FM_MULTI_CASE
-    PlaceArgs sum{};   // place_sum_kernel with an entry in a query's place
-    sum.nq = a.nnz; sum.parts = a.parts; sum.part = a.part; sum.counts = a.counts;
-    int L = 1;
-    while (L < kWave && L < a.parts) L <<= 1;
-    hipLaunchKernelGGL(place_sum_kernel, grid(a.nnz * L), dim3(kPlaceThreads), 0, st, sum, L);
+    if (dispatch_groups(a.Kp, [&](auto j) {
+          hipLaunchKernelGGL((multi_count_kernel<decltype(j)::value>), dim3((unsigned)blocks), dim3(kPlaceThreads), 0,
+                             st, a, rblocks);
+        }))
+      return -1;
+    launch_place_sum(a.part, a.counts, a.nnz, a.parts, st);
     if (sn)
       hipLaunchKernelGGL(multi_seen_kernel, grid(a.nnz * kMultiSeenLanes), dim3(kPlaceThreads), 0, st, a, *sn);
     if (hipGetLastError() != hipSuccess) return -3;

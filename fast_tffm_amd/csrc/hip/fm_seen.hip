@@ -1,7 +1,7 @@
 // Recommend and place with every query's already-seen candidates left out (the standard leave-one-out protocol
 // ranks the held-out item among the items the user has not interacted with; the reference only scores examples).
 //
-// A seen list per query is a CSR pair (SeenArgs, fm_topk.hip): off int32 [nq + 1], idx int32 [nnz], a query's
+// A seen list per query is a CSR pair (SeenArgs, fm_rank_common.h): off int32 [nq + 1], idx int32 [nnz], a query's
 // indices strictly ascending in [0, nc).  E_q is query q's set; the score s(q, c) is fm_topk.hip's, bit for bit.
 //   top-k: row q holds the k greatest keys over c not in E_q (-1 / -inf where fewer than k remain);
 //   place: greater / equal count the c not in E_q \ {t} -- the query's own target always competes.
@@ -21,41 +21,24 @@
 // 2. place_seen_kernel: a correction after place_sum_kernel; the matrix-core count pass is untouched.  Counts over
 //    all candidates minus counts over the seen ones is exact, both being integers over the same exact fp32 scores.
 //    A group of 16 lanes takes one query (four queries to a wave) and strides over its list; a lane computes
-//    s(q, e) with place_target_kernel's fmaf chain in pi's order from 16-byte row fragments -- the chain the matrix
+//    s(q, e) with score_chain (fm_rank_common.h), as place_target_kernel does -- the chain the matrix
 //    instruction is -- compares it with s_t from the workspace, and skips e == target[q]; unranked queries are
 //    skipped whole.  The group's (greater, equal) are added across its lanes in a fixed pattern and its first lane
 //    subtracts them from counts[q]: one writer per query, no atomics, no host read.  A long list is walked by its
 //    16 lanes.  Compiled, like the other fp32 score kernels of fm_place.hip, without the packed fp32 instructions.
 //
-// (Included by module.hip after fm_place.hip -- PlaceArgs, FM_PLACE_FN.)  Graph-capturable and bitwise repeatable.
-#include "fm_common.h"
+// (Included by module.hip after fm_topk.hip and fm_place.hip, whose kernels and arguments these passes extend.)
+// Graph-capturable and bitwise repeatable.
+#include "fm_rank_common.h"
 
 namespace fm {
 
-inline bool seen_args_ok(const SeenArgs& sn) { return sn.off && sn.nnz >= 0 && (sn.idx || sn.nnz == 0); }
-
 // launch_topk with the lists `sn`: the same plan, workspace and merge pass.
-inline int launch_topk_seen(TopkArgs a, SeenArgs sn, hipStream_t stream) {
-  long long qtiles = 0, blocks = 0;
-  if (topk_prepare(a, qtiles, blocks) || !seen_args_ok(sn)) return -1;
-  if (a.nq == 0) return 0;
-  const int kc1 = topk_kcap(a.k, 32);
-  const size_t lds1 = topk_lds_bytes(topk::kTile, kc1);
-#define FM_SEEN_CASE(JJ)                                                                                     \
-  case JJ:                                                                                                   \
-    hipLaunchKernelGGL((topk_slab_kernel<JJ, true>), dim3((unsigned)blocks), dim3(kWave), lds1, stream, a, qtiles, \
-                       kc1, so);                                                                             \
-    break;
+inline int launch_topk_seen(const TopkArgs& a, SeenArgs sn, hipStream_t stream) {
+  if (!seen_args_ok(sn)) return -1;
   SeenOpt<true> so;
   static_cast<SeenArgs&>(so) = sn;
-  switch (topk::groups(a.Kp)) {
-    FM_SEEN_CASE(1) FM_SEEN_CASE(2) FM_SEEN_CASE(3) FM_SEEN_CASE(4) FM_SEEN_CASE(5) FM_SEEN_CASE(6)
-    FM_SEEN_CASE(7) FM_SEEN_CASE(8) FM_SEEN_CASE(9) FM_SEEN_CASE(10) FM_SEEN_CASE(11) FM_SEEN_CASE(12)
-    FM_SEEN_CASE(13) FM_SEEN_CASE(14) FM_SEEN_CASE(15) FM_SEEN_CASE(16)
-    default: return -1;
-  }
-#undef FM_SEEN_CASE
-  return launch_topk_merge(a, stream);
+  return launch_topk_slabs<true>(a, so, stream);
 }
 
 constexpr int kSeenLanes = 16;  // lanes per query of place_seen_kernel
@@ -67,35 +50,15 @@ __global__ FM_PLACE_FN __launch_bounds__(kPlaceThreads) void place_seen_kernel(P
   const bool ranked = q < a.nq && a.flag[q] != 0;   // (uniform over the 16 lanes)
   int gt = 0, eq = 0;
   if (ranked) {
-    const int o0 = sn.off[q], o1 = sn.off[q + 1];
-    const int b0 = o0 < 0 ? 0 : o0 > sn.nnz ? sn.nnz : o0;
-    const int e0 = o1 < b0 ? b0 : o1 > sn.nnz ? sn.nnz : o1;
+    int b0, e0;
+    csr_window(sn.off, sn.nnz, q, b0, e0);
     const int t = a.target[q];
     const float stq = a.st[q], qbq = a.qb[q];
     const float* qr = a.Q + q * a.q_stride;
-    const int G = (a.Kp + topk::kGroup - 1) / topk::kGroup;
     for (int p = b0 + sub; p < e0; p += kSeenLanes) {
       const int c = sn.idx[p];
       if (c < 0 || c >= a.nc || c == t) continue;
-      const float* cr = a.C + (long long)c * a.c_stride;
-      float dot = 0.f;
-      for (int g = 0; g < G; ++g) {
-        // the group's 4 fragments of both rows (zeros past Kp: fmaf(0, 0, dot) == dot, ../topk_order.h)
-        f32x4 qf[4], cf[4];
-#pragma unroll
-        for (int h = 0; h < 4; ++h) {
-          qf[h] = cf[h] = f32x4{0.f, 0.f, 0.f, 0.f};
-          if (topk::kGroup * g + 4 * h < a.Kp) {
-            qf[h] = *reinterpret_cast<const f32x4*>(qr + topk::kGroup * g + 4 * h);
-            cf[h] = *reinterpret_cast<const f32x4*>(cr + topk::kGroup * g + 4 * h);
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e)
-#pragma unroll
-          for (int h = 0; h < 4; ++h) dot = __builtin_fmaf(qf[h][e], cf[h][e], dot);
-      }
-      const float s = ((qbq + a.cb[c]) + dot) + 0.f;
+      const float s = score_of(qbq, a.cb[c], score_chain(qr, a.C + (long long)c * a.c_stride, a.Kp));
       gt += (int)(s > stq);
       eq += (int)(s == stq);
     }

@@ -1,7 +1,7 @@
 // Recommend and place among every query's own shortlist of candidates (re-ranking what a retrieval stage handed
 // over; the sampled-negative leave-one-out protocol.  The reference only scores examples).
 //
-// A shortlist per query is the CSR pair of fm_seen.hip (SeenArgs): off int32 [nq + 1], idx int32 [nnz], a query's
+// A shortlist per query is a CSR pair (SeenArgs, fm_rank_common.h): off int32 [nq + 1], idx int32 [nnz], a query's
 // indices strictly ascending in [0, nc).  L_q is query q's set; the score s(q, c) is fm_topk.hip's, bit for bit.
 //   top-k: row q holds the k greatest keys over c in L_q (-1 / -inf where |L_q| < k);
 //   place: the competitors are L_q and the target t: greater = #{c in L_q, c != t : s(q, c) > s_t},
@@ -13,7 +13,7 @@
 // `parts` runs of whole 64-entry steps (../topk_order.h: shortlist_plan, shortlist_run), so most parts of a short
 // list are empty -- and still write their k zero keys / zero counts: the passes behind read every slot and the
 // workspace is never cleared.  The wave keeps the query's A operands in registers for the whole walk, in
-// fm_topk.hip's layout (lane (r, h): columns 16 g + 4 h .. + 3) -- the same query in all 16 rows of the tile.  A
+// load_operands' layout (lane (r, h): columns 16 g + 4 h .. + 3) -- the same query in all 16 rows of the tile.  A
 // step takes 64 list entries: one coalesced load of 64 indices (lane l: entry l), then four 16-candidate tiles;
 // for tile t lane (r, h) fetches the index of entry 16 t + r from its lane and loads 16 bytes per column group of
 // that candidate's row straight from C -- four lanes cover 64 contiguous bytes of a row, 16 rows per instruction
@@ -24,9 +24,9 @@
 // step i + 2 and the row gathers of step i + 1 are issued before step i is multiplied and ranked, so the gathers
 // -- the walk's bound -- are in flight under it; wider profiles gather in place (in two halves above Kp = 128, to
 // stay in registers) and lean on the other waves of the SIMD.
-// Select epilogue (COUNT = false): topk_merge_kernel's selection on one row -- a lane whose key beats the current
-// k-th key is found by ballot and appended to an LDS buffer of 2 kcap keys (kcap = max(64, pow2 >= k)), cut to k by
-// topk_compact_rows when it passes kcap -- and the k keys go to ws[(q parts + part) k ..], fm_topk's workspace
+// Select epilogue (COUNT = false): select_append_row, topk_merge_kernel's selection on one row -- a lane whose key
+// beats the current k-th key is found by ballot and appended to an LDS buffer of 2 kcap keys (kcap = max(64, pow2 >=
+// k)), cut to k when it passes kcap -- and the k keys go to ws[(q parts + part) k ..], fm_topk's workspace
 // layout: topk_merge_kernel with a.parts = this plan's parts finishes the job unchanged.
 // Count epilogue (COUNT = true): after place_target_kernel; a lane compares its score with s_t, skipping c == t,
 // the wave's two int32 sums are added across lanes in a fixed pattern and lane 0 writes the (query, part) partial,
@@ -34,19 +34,15 @@
 // run unchanged on this call's parts; the count pass over the catalogue is not launched.
 // A single huge list among many short ones walks on one wave per part: correct, but slow.
 //
-// (Included by module.hip after fm_seen.hip.)  No atomics, no host read, no allocation; graph-capturable and
+// (Included by module.hip after fm_topk.hip and fm_place.hip, whose merge, target, sum and metric passes it
+// launches.)  No atomics, no host read, no allocation; graph-capturable and
 // bitwise repeatable.
-#include "fm_common.h"
+#include "fm_rank_common.h"
 
 namespace fm {
 
-struct ShortlistArgs {
-  long long nq, nc;
-  int Kp, k;
-  const float* Q; long long q_stride;   // [nq, Kp], row stride in elements (16-byte aligned rows)
-  const float* C; long long c_stride;   // [nc, Kp]
-  const float* qb;                      // [nq]
-  const float* cb;                      // [nc]
+struct ShortlistArgs : ProfileArgs {
+  int k;
   SeenArgs sl;                          // the lists
   int parts;                            // topk::shortlist_plan
   unsigned long long* ws;               // select: [nq][parts][k] keys
@@ -69,10 +65,9 @@ __global__ __launch_bounds__(kWave) void shortlist_kernel(ShortlistArgs a, int k
   const long long q = b / a.parts;
   const int part = (int)(b - q * a.parts);
 
-  // this part's run [pb, pe) of the query's window (clamped to [0, nnz])
-  const int o0 = a.sl.off[q], o1 = a.sl.off[q + 1];
-  const int b0 = o0 < 0 ? 0 : o0 > a.sl.nnz ? a.sl.nnz : o0;
-  const int e0 = o1 < b0 ? b0 : o1 > a.sl.nnz ? a.sl.nnz : o1;
+  // this part's run [pb, pe) of the query's window
+  int b0, e0;
+  csr_window(a.sl.off, a.sl.nnz, q, b0, e0);
   const long long run = topk::shortlist_run((long long)e0 - b0, a.parts);
   const long long pb = b0 + part * run;
   const long long pe = pb + run < e0 ? pb + run : e0;
@@ -98,16 +93,9 @@ __global__ __launch_bounds__(kWave) void shortlist_kernel(ShortlistArgs a, int k
     return;
   }
 
-  // A operands: the query's columns 16 g + 4 h .. + 3 (zeros past Kp), the same in all 16 rows
+  // A operands: the query's row (load_operands), the same in all 16 rows
   f32x4 qa[J];
-  {
-    const float* qp = a.Q + q * a.q_stride + 4 * h;
-#pragma unroll
-    for (int g = 0; g < J; ++g) {
-      qa[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (topk::col(g, 0, h) < a.Kp) qa[g] = *reinterpret_cast<const f32x4*>(qp + topk::kGroup * g);
-    }
-  }
+  load_operands<J>(a.Q + q * a.q_stride + 4 * h, h, a.Kp, qa);
   const float qbq = a.qb[q];
 
   // this lane's candidate of the step at p0: entry p0 + lane, -1 past the run's end or outside [0, nc)
@@ -127,12 +115,7 @@ __global__ __launch_bounds__(kWave) void shortlist_kernel(ShortlistArgs a, int k
 #pragma unroll
     for (int t = 0; t < NT; ++t) {
       const int ct = __builtin_amdgcn_ds_bpermute((topk::kTile * (T0 + t) + r) << 2, cl);
-      const float* cp = a.C + (long long)(ct < 0 ? 0 : ct) * a.c_stride + 4 * h;
-#pragma unroll
-      for (int g = 0; g < J; ++g) {
-        v[t][g] = f32x4{0.f, 0.f, 0.f, 0.f};
-        if (ct >= 0 && topk::col(g, 0, h) < a.Kp) v[t][g] = *reinterpret_cast<const f32x4*>(cp + topk::kGroup * g);
-      }
+      load_operands<J>(a.C + (long long)(ct < 0 ? 0 : ct) * a.c_stride + 4 * h, h, a.Kp, v[t], ct >= 0);
     }
   };
   // acc[T0 + t] += the tiles' products, the accumulators independent of each other
@@ -204,23 +187,14 @@ __global__ __launch_bounds__(kWave) void shortlist_kernel(ShortlistArgs a, int k
     }
     // tile h's score in this lane's column r: entry 16 h + r, this lane's own
     const float dot = h == 0 ? acc[0][0] : h == 1 ? acc[1][0] : h == 2 ? acc[2][0] : acc[3][0];
-    const float s = ((qbq + cbv) + dot) + 0.f;
+    const float s = score_of(qbq, cbv, dot);
     if constexpr (COUNT) {
       const bool on = c >= 0 && c != tq;
       gt += (int)(on && s > stq);
       eq += (int)(on && s == stq);
     } else {
       const unsigned long long key = c >= 0 ? topk::make_key(__float_as_uint(s), (uint32_t)c) : 0ull;
-      const bool win = key > thr;  // (an absent entry is 0 and never wins)
-      const unsigned long long m = __ballot(win);
-      if (m != 0ull) {
-        if (win) buf[*cnt_s + __popcll(m & ((1ull << lane) - 1ull))] = key;
-        __syncthreads();
-        if (lane == 0) *cnt_s += __popcll(m);
-        __syncthreads();
-        if (*cnt_s > kcap) topk_compact_rows(buf, cap, a.k, 1, cnt_s, thr_s, lane);
-        thr = *thr_s;
-      }
+      thr = select_append_row(buf, cnt_s, thr_s, key, thr, kcap, a.k, lane);
     }
   }
 
@@ -246,14 +220,10 @@ __global__ __launch_bounds__(kWave) void shortlist_kernel(ShortlistArgs a, int k
 inline long long shortlist_select_bytes(long long nq, int parts, int k) {
   return nq * parts * k * (long long)sizeof(unsigned long long);
 }
-// [tiles][s_t][flag][parts]: launch_place's layout on this call's parts
-inline long long shortlist_count_bytes(long long nq, int parts, int nk) {
-  return place_metrics_workspace_bytes(nq, nk) + place_pad8(nq * 4) * 2 + nq * parts * 8;
-}
 // Workspace bytes that serve both a top-k call of k results and a place call of any cutoffs on lists of nnz entries.
 inline long long shortlist_workspace_bytes(long long nq, long long nnz, long long nc, int k) {
   const int parts = topk::shortlist_plan(nq, nnz, nc);
-  const long long s = shortlist_select_bytes(nq, parts, k), c = shortlist_count_bytes(nq, parts, kRankMaxCutoffs);
+  const long long s = shortlist_select_bytes(nq, parts, k), c = place_layout_bytes(nq, parts, kRankMaxCutoffs);
   return s > c ? s : c;
 }
 
@@ -263,17 +233,11 @@ inline int launch_shortlist_walk(const ShortlistArgs& a, hipStream_t stream) {
   if (blocks >= (1ll << 31)) return -1;
   const int kc = COUNT ? 0 : topk_kcap(a.k, kWave);
   const size_t lds = COUNT ? 0 : topk_lds_bytes(1, kc);
-#define FM_SHORT_CASE(JJ)                                                                                       \
-  case JJ:                                                                                                      \
-    hipLaunchKernelGGL((shortlist_kernel<JJ, COUNT>), dim3((unsigned)blocks), dim3(kWave), lds, stream, a, kc); \
-    break;
-  switch (topk::groups(a.Kp)) {
-    FM_SHORT_CASE(1) FM_SHORT_CASE(2) FM_SHORT_CASE(3) FM_SHORT_CASE(4) FM_SHORT_CASE(5) FM_SHORT_CASE(6)
-    FM_SHORT_CASE(7) FM_SHORT_CASE(8) FM_SHORT_CASE(9) FM_SHORT_CASE(10) FM_SHORT_CASE(11) FM_SHORT_CASE(12)
-    FM_SHORT_CASE(13) FM_SHORT_CASE(14) FM_SHORT_CASE(15) FM_SHORT_CASE(16)
-    default: return -1;
-  }
-#undef FM_SHORT_CASE
+  if (dispatch_groups(a.Kp, [&](auto j) {
+        hipLaunchKernelGGL((shortlist_kernel<decltype(j)::value, COUNT>), dim3((unsigned)blocks), dim3(kWave), lds,
+                           stream, a, kc);
+      }))
+    return -1;
   return hipGetLastError() == hipSuccess ? 0 : -3;
 }
 
@@ -285,8 +249,8 @@ inline int launch_topk_shortlist(TopkArgs a, SeenArgs sl, size_t ws_bytes, hipSt
   a.parts = topk::shortlist_plan(a.nq, sl.nnz, a.nc);
   if ((long long)ws_bytes < shortlist_select_bytes(a.nq, a.parts, a.k)) return -2;
   ShortlistArgs s{};
-  s.nq = a.nq; s.nc = a.nc; s.Kp = a.Kp; s.k = a.k; s.Q = a.Q; s.q_stride = a.q_stride; s.C = a.C;
-  s.c_stride = a.c_stride; s.qb = a.qb; s.cb = a.cb; s.sl = sl; s.parts = a.parts; s.ws = a.ws;
+  static_cast<ProfileArgs&>(s) = a;
+  s.k = a.k; s.sl = sl; s.parts = a.parts; s.ws = a.ws;
   if (const int rc = launch_shortlist_walk<false>(s, stream)) return rc;
   return launch_topk_merge(a, stream);
 }
@@ -294,31 +258,20 @@ inline int launch_topk_shortlist(TopkArgs a, SeenArgs sl, size_t ws_bytes, hipSt
 // counts [nq, 2] and the record of nq >= 1 queries, each against its list `sl` and its target.  Codes as launch_place.
 inline int launch_place_shortlist(PlaceArgs a, SeenArgs sl, const int* k, int nk, void* rec, void* ws, size_t ws_bytes,
                                   hipStream_t st) {
-  if (a.Kp < 4 || a.Kp > topk::kMaxKp || a.Kp % 4 || a.nq < 1 || a.nc < 1 || a.nc >= (1ll << 31) ||
-      a.nq >= (1ll << 31) || !a.Q || !a.C || !a.qb || !a.cb || !a.target || !a.counts || !ws ||
-      (reinterpret_cast<uintptr_t>(ws) & 7) || !seen_args_ok(sl))
-    return -1;
+  if (!place_args_ok(a, ws) || !seen_args_ok(sl)) return -1;
   if (!rank_cutoffs_ok(k, nk)) return -7;
   a.parts = topk::shortlist_plan(a.nq, sl.nnz, a.nc);
-  if ((long long)ws_bytes < shortlist_count_bytes(a.nq, a.parts, nk)) return -2;
-  char* base = static_cast<char*>(ws);
-  const long long mbytes = place_metrics_workspace_bytes(a.nq, nk);
-  a.st = reinterpret_cast<float*>(base + mbytes);
-  a.flag = reinterpret_cast<int*>(base + mbytes + place_pad8(a.nq * 4));
-  a.part = reinterpret_cast<int*>(base + mbytes + 2 * place_pad8(a.nq * 4));
+  if ((long long)ws_bytes < place_layout_bytes(a.nq, a.parts, nk)) return -2;
+  place_carve(a, ws, nk);
   const unsigned qgrid = (unsigned)((a.nq + kPlaceThreads - 1) / kPlaceThreads);
   hipLaunchKernelGGL(place_target_kernel, dim3(qgrid), dim3(kPlaceThreads), 0, st, a);
   ShortlistArgs s{};
-  s.nq = a.nq; s.nc = a.nc; s.Kp = a.Kp; s.k = 0; s.Q = a.Q; s.q_stride = a.q_stride; s.C = a.C;
-  s.c_stride = a.c_stride; s.qb = a.qb; s.cb = a.cb; s.sl = sl; s.parts = a.parts; s.target = a.target;
-  s.st = a.st; s.flag = a.flag; s.part = a.part;
+  static_cast<ProfileArgs&>(s) = a;
+  s.sl = sl; s.parts = a.parts; s.target = a.target; s.st = a.st; s.flag = a.flag; s.part = a.part;
   if (const int rc = launch_shortlist_walk<true>(s, st)) return rc;
-  int L = 1;
-  while (L < kWave && L < a.parts) L <<= 1;
-  const long long sum_threads = a.nq * L;
-  hipLaunchKernelGGL(place_sum_kernel, dim3((unsigned)((sum_threads + kPlaceThreads - 1) / kPlaceThreads)),
-                     dim3(kPlaceThreads), 0, st, a, L);
+  launch_place_sum(a.part, a.counts, a.nq, a.parts, st);
   if (hipGetLastError() != hipSuccess) return -3;
+  const long long mbytes = place_metrics_workspace_bytes(a.nq, nk);
   return launch_place_metrics(a.counts, a.nq, k, nk, rec, mbytes ? ws : nullptr, (size_t)mbytes, st);
 }
 

@@ -24,90 +24,19 @@
 // No host synchronisation, no allocation: the workspace comes from the caller (graph-capturable).
 // topk_slab_kernel<J, true> (fm_seen.hip) is the same pass with each query's already-seen candidates left out; the
 // plain instantiation takes no list and has no instruction for it.
-#include "fm_common.h"
-#include "../topk_order.h"
+// The operand load, the score and the LDS selection are fm_rank_common.h's, shared with the other
+// ranking kernels.
+#include "fm_rank_common.h"
 
 namespace fm {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-struct TopkArgs {
-  long long nq, nc;
-  int Kp, k;
-  const float* Q; long long q_stride;   // [nq, Kp], row stride in elements (16-byte aligned rows)
-  const float* C; long long c_stride;   // [nc, Kp]
-  const float* qb;                      // [nq]
-  const float* cb;                      // [nc]
+struct TopkArgs : ProfileArgs {
+  int k;
   long long slab; int parts;            // topk::plan
   unsigned long long* ws;               // [nq][parts][k] keys
   int* idx;                             // [nq, k]
   float* score;                         // [nq, k]
 };
-
-inline int topk_kcap(int k, int floor_) { return next_pow2(k < floor_ ? floor_ : k); }
-inline size_t topk_lds_bytes(int rows, int kcap) {
-  return (size_t)rows * (2 * kcap) * sizeof(unsigned long long) + rows * (sizeof(unsigned long long) + sizeof(int));
-}
-
-// Sort each of `rows` consecutive buffers of cap keys descending, all in the same passes (cap a power of two
-// >= 2); every lane of the single-wave workgroup calls.
-__device__ inline void topk_sort_rows(unsigned long long* buf, int cap, int rows, int lane) {
-  const int half = cap >> 1;          // compare-exchanges per row and pass
-  const int hs = __ffs(half) - 1;     // log2(half)
-  for (int size = 2; size <= cap; size <<= 1) {
-    for (int stride = size >> 1; stride > 0; stride >>= 1) {
-      for (int t = lane; t < rows * half; t += kWave) {
-        const int tt = t & (half - 1);
-        const int i = 2 * tt - (tt & (stride - 1));
-        unsigned long long* rb = buf + (t >> hs) * cap;
-        const bool desc = (i & size) == 0;
-        const unsigned long long x = rb[i], y = rb[i + stride];
-        if ((x < y) == desc) {
-          rb[i] = y;
-          rb[i + stride] = x;
-        }
-      }
-      __syncthreads();
-    }
-  }
-}
-
-// Sort `rows` buffers (cnt[row] entries each, the rest zeroed first) and cut every one that holds k or more
-// keys to its best k: its count becomes k and its threshold the k-th key.  Wave-uniform call.
-__device__ inline void topk_compact_rows(unsigned long long* buf, int cap, int k, int rows, int* cnt,
-                                         unsigned long long* thr, int lane) {
-  const int cs = __ffs(cap) - 1;
-  __syncthreads();
-  for (int t = lane; t < rows * cap; t += kWave)
-    if ((t & (cap - 1)) >= cnt[t >> cs]) buf[t] = 0ull;
-  __syncthreads();
-  topk_sort_rows(buf, cap, rows, lane);
-  if (lane < rows && cnt[lane] >= k) {
-    cnt[lane] = k;
-    thr[lane] = buf[lane * cap + k - 1];
-  }
-  __syncthreads();
-}
-
-// Per-query lists of candidates to leave out (fm_seen.hip): CSR, a query's indices strictly ascending in [0, nc).
-struct SeenArgs {
-  const int* off;   // [nq + 1]
-  const int* idx;   // [nnz]
-  int nnz;
-};
-
-// The first position p of [lo, hi) with idx[p] >= v (hi if none).  Reads stay inside [lo, hi) whatever the order.
-__device__ inline int seen_lower_bound(const int* idx, int lo, int hi, int v) {
-  while (lo < hi) {
-    const int mid = lo + ((hi - lo) >> 1);
-    if (idx[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
-}
-__device__ inline bool seen_contains(const int* idx, int lo, int hi, int v) {
-  const int p = seen_lower_bound(idx, lo, hi, v);
-  return p < hi && idx[p] == v;
-}
 
 // The lists as a kernel argument: nothing at all for the plain instantiation.
 template <bool SEEN> struct SeenOpt {};
@@ -138,16 +67,11 @@ __global__ __launch_bounds__(kWave) void topk_slab_kernel(TopkArgs a, long long 
   }
   __syncthreads();
 
-  // A operands: query row q0 + r, columns 16 g + 4 h .. + 3 (zeros past Kp)
+  // A operands: query row q0 + r (load_operands)
   f32x4 qa[J];
   {
     const long long qr = q0 + r < a.nq ? q0 + r : a.nq - 1;
-    const float* qp = a.Q + qr * a.q_stride + 4 * h;
-#pragma unroll
-    for (int g = 0; g < J; ++g) {
-      qa[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (topk::col(g, 0, h) < a.Kp) qa[g] = *reinterpret_cast<const f32x4*>(qp + topk::kGroup * g);
-    }
+    load_operands<J>(a.Q + qr * a.q_stride + 4 * h, h, a.Kp, qa);
   }
   // this lane's 4 result rows: queries q0 + 4 h + i
   float qbv[4];
@@ -160,16 +84,14 @@ __global__ __launch_bounds__(kWave) void topk_slab_kernel(TopkArgs a, long long 
     qbv[i] = qok[i] ? a.qb[q] : 0.f;
     thr[i] = 0ull;
   }
-  // SEEN: the part [slo, shi) of each of this lane's rows' lists that lies inside the slab (the list's window
-  // clamped to [0, nnz]: a malformed list cannot lead a read out of bounds)
+  // SEEN: the part [slo, shi) of each of this lane's rows' lists that lies inside the slab
   int slo[4] = {0, 0, 0, 0}, shi[4] = {0, 0, 0, 0};
   if constexpr (SEEN) {
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (!qok[i]) continue;
-      const int o0 = sn.off[q0 + 4 * h + i], o1 = sn.off[q0 + 4 * h + i + 1];
-      const int b0 = o0 < 0 ? 0 : o0 > sn.nnz ? sn.nnz : o0;
-      const int e0 = o1 < b0 ? b0 : o1 > sn.nnz ? sn.nnz : o1;
+      int b0, e0;
+      csr_window(sn.off, sn.nnz, q0 + 4 * h + i, b0, e0);
       slo[i] = seen_lower_bound(sn.idx, b0, e0, (int)c_begin);
       shi[i] = seen_lower_bound(sn.idx, slo[i], e0, (int)c_end);
     }
@@ -180,16 +102,8 @@ __global__ __launch_bounds__(kWave) void topk_slab_kernel(TopkArgs a, long long 
   const auto load_pair = [&](long long c0, f32x4 (&va)[J], f32x4 (&vb)[J], float& cba, float& cbb) {
     const long long ca = c0 + r, cbi = c0 + topk::kTile + r;
     const long long la = ca < c_end ? ca : c_end - 1, lb = cbi < c_end ? cbi : c_end - 1;
-    const float* pa = a.C + la * a.c_stride + 4 * h;
-    const float* pb = a.C + lb * a.c_stride + 4 * h;
-#pragma unroll
-    for (int g = 0; g < J; ++g) {
-      va[g] = vb[g] = f32x4{0.f, 0.f, 0.f, 0.f};
-      if (topk::col(g, 0, h) < a.Kp) {
-        va[g] = *reinterpret_cast<const f32x4*>(pa + topk::kGroup * g);
-        vb[g] = *reinterpret_cast<const f32x4*>(pb + topk::kGroup * g);
-      }
-    }
+    load_operands<J>(a.C + la * a.c_stride + 4 * h, h, a.Kp, va);
+    load_operands<J>(a.C + lb * a.c_stride + 4 * h, h, a.Kp, vb);
     cba = a.cb[la];
     cbb = a.cb[lb];
   };
@@ -236,7 +150,7 @@ __global__ __launch_bounds__(kWave) void topk_slab_kernel(TopkArgs a, long long 
       bool any = false;
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
-        const float s = ((qbv[i] + cbv) + acc[i]) + 0.f;
+        const float s = score_of(qbv[i], cbv, acc[i]);
         key[i] = topk::make_key(__float_as_uint(s), c32);
         win[i] = cok && qok[i] && key[i] > thr[i];
         any = any || win[i];
@@ -311,16 +225,7 @@ __global__ __launch_bounds__(kWave) void topk_merge_kernel(TopkArgs a, int kcap)
   unsigned long long thr = 0ull;
   for (long long t0 = 0; t0 < n; t0 += kWave) {
     const long long t = t0 + lane;
-    const unsigned long long key = t < n ? in[t] : 0ull;
-    const bool win = key > thr;  // (an empty place is 0 and never wins)
-    const unsigned long long m = __ballot(win);
-    if (m == 0ull) continue;
-    if (win) buf[*cnt_s + __popcll(m & ((1ull << lane) - 1ull))] = key;
-    __syncthreads();
-    if (lane == 0) *cnt_s += __popcll(m);
-    __syncthreads();
-    if (*cnt_s > kcap) topk_compact_rows(buf, cap, a.k, 1, cnt_s, thr_s, lane);
-    thr = *thr_s;
+    thr = select_append_row(buf, cnt_s, thr_s, t < n ? in[t] : 0ull, thr, kcap, a.k, lane);
   }
   topk_compact_rows(buf, cap, a.k, 1, cnt_s, thr_s, lane);
   for (int t = lane; t < a.k; t += kWave) {
@@ -338,15 +243,13 @@ inline long long topk_workspace_bytes(long long nq, long long nc, int k) {
 
 // Checks a call's sizes and fills in its plan and phase 1's grid (shared with fm_seen.hip).  -1: bad arguments.
 inline int topk_prepare(TopkArgs& a, long long& qtiles, long long& blocks) {
-  if (a.k < 1 || a.k > topk::kMaxK || a.Kp < 4 || a.Kp > topk::kMaxKp || a.Kp % 4 || a.nq < 0 || a.nc < 0 ||
-      a.nc >= (1ll << 31))
-    return -1;
+  if (a.k < 1 || a.k > topk::kMaxK || !profile_args_ok(a)) return -1;
   const topk::Plan p = topk::plan(a.nq, a.nc, a.k);
   a.slab = p.slab;
   a.parts = p.parts;
   qtiles = (a.nq + topk::kTile - 1) / topk::kTile;
   blocks = qtiles * a.parts;
-  return blocks >= (1ll << 31) || a.nq >= (1ll << 31) ? -1 : 0;
+  return blocks >= (1ll << 31) ? -1 : 0;
 }
 
 inline int launch_topk_merge(const TopkArgs& a, hipStream_t stream) {
@@ -355,25 +258,24 @@ inline int launch_topk_merge(const TopkArgs& a, hipStream_t stream) {
   return hipGetLastError() == hipSuccess ? 0 : -2;
 }
 
-inline int launch_topk(TopkArgs a, hipStream_t stream) {
+// Both phases of a call; `sn`: the lists to leave out (fm_seen.hip) or nothing.
+template <bool SEEN>
+inline int launch_topk_slabs(TopkArgs a, SeenOpt<SEEN> sn, hipStream_t stream) {
   long long qtiles = 0, blocks = 0;
   if (topk_prepare(a, qtiles, blocks)) return -1;
   if (a.nq == 0) return 0;
   const int kc1 = topk_kcap(a.k, 32);
   const size_t lds1 = topk_lds_bytes(topk::kTile, kc1);
-#define FM_TOPK_CASE(JJ)                                                                                       \
-  case JJ:                                                                                                     \
-    hipLaunchKernelGGL((topk_slab_kernel<JJ>), dim3((unsigned)blocks), dim3(kWave), lds1, stream, a, qtiles, kc1, \
-                       SeenOpt<false>{});                                                                      \
-    break;
-  switch (topk::groups(a.Kp)) {
-    FM_TOPK_CASE(1) FM_TOPK_CASE(2) FM_TOPK_CASE(3) FM_TOPK_CASE(4) FM_TOPK_CASE(5) FM_TOPK_CASE(6)
-    FM_TOPK_CASE(7) FM_TOPK_CASE(8) FM_TOPK_CASE(9) FM_TOPK_CASE(10) FM_TOPK_CASE(11) FM_TOPK_CASE(12)
-    FM_TOPK_CASE(13) FM_TOPK_CASE(14) FM_TOPK_CASE(15) FM_TOPK_CASE(16)
-    default: return -1;
-  }
-#undef FM_TOPK_CASE
+  if (dispatch_groups(a.Kp, [&](auto j) {
+        hipLaunchKernelGGL((topk_slab_kernel<decltype(j)::value, SEEN>), dim3((unsigned)blocks), dim3(kWave), lds1,
+                           stream, a, qtiles, kc1, sn);
+      }))
+    return -1;
   return launch_topk_merge(a, stream);
+}
+
+inline int launch_topk(const TopkArgs& a, hipStream_t stream) {
+  return launch_topk_slabs<false>(a, SeenOpt<false>{}, stream);
 }
 
 }  // namespace fm
